@@ -12,10 +12,18 @@ A "step" is one pass of the hot path over one batch of synthetic input:
   q5: the 6-way join (customer/orders/lineitem/supplier/nation/region,
       local-supplier condition, per-nation revenue).
 
-The default invocation (--query all) measures q1, q3 and q5 back to back
-and prints ONE JSON line per query plus a final combined line for the
-BASELINE metric, which names "TPC-H SF100 Q1 & Q3": the combined value is
+The default invocation (--query all) does only what the headline figure
+needs: it measures q1 and q3 and prints ONE JSON line, the combined line for
+the BASELINE metric, which names "TPC-H SF100 Q1 & Q3": the combined value is
 lineitem rows/s over one Q1 pass + one Q3 pass per step.
+
+--full adds everything else: the q5 leg, the CPU-oracle baselines, one JSON
+line per query ahead of the combined line, and (with --verify) the full-size
+comparison against the CPU oracle.
+
+--dump-outputs DIR writes what the last timed step of each query returned,
+one DIR/<query>.<column>.npy per output column (float32/float64), so that two
+builds can be compared output for output: inputs depend on the arguments only.
 
 Inputs are synthetic TPC-H columns from the dbgen restatement in
 oracle/tpchgen.c (golden-pinned; generation is test/bench input
@@ -28,8 +36,8 @@ partials combined in rank order (the partial->final Step split of
 HashAggregationOperator.java:72); Q3/Q5 exchange by orderkey hash over
 RCCL all_to_all (presto_amd/dist.py) before local build/probe.
 
-cpu_baseline: the CPU oracle (oracle/liboracle.so, kind "port") timed on
-this box's host cores over a bounded sample — reported baseline only, never
+cpu_baseline (--full only): the CPU oracle (oracle/liboracle.so, kind "port")
+timed on the host cores over a bounded sample — reported baseline only, never
 the measured value.
 """
 import argparse
@@ -293,9 +301,10 @@ class Bench:
             from presto_amd import dist as pdist
             pdist.exchange_bytes_reset()
         self.barrier_sync()
+        out = None
         t0 = time.time()
         for _ in range(a.steps):
-            step()
+            out = step()
         self.barrier_sync()
         elapsed = time.time() - t0
         if self.world > 1:
@@ -310,7 +319,7 @@ class Bench:
             dist.all_reduce(e, op=dist.ReduceOp.MAX)
             elapsed = float(e.item())
         hot_ms = float(self.lib.c.pg_hot_max_ms())
-        return elapsed, hot_ms
+        return elapsed, hot_ms, out
 
     def total_rows(self, n_local):
         if self.world > 1:
@@ -455,10 +464,59 @@ def traffic_for(query, mode, sf):
         return None
 
 
+DUMP_BUDGET = 64 << 20  # bytes over all files of one --dump-outputs run
+
+
+def dump_outputs(outdir, outs):
+    """Write the last timed step's return value of every measured query as
+    outdir/<query>.<column>.npy, float32 for columns of up to 2 bytes per
+    value, float64 for the rest.  An 8-byte integer column that float64
+    cannot hold exactly (the low word of a 128-bit decimal sum) is also
+    written as its exact 32-bit halves, <column>.hi32 (signed) and
+    <column>.lo32.  A column over its share of DUMP_BUDGET is cut to a
+    fixed, seeded sample of its rows."""
+    outdir = pathlib.Path(outdir)
+    outdir.mkdir(parents=True, exist_ok=True)
+    arrays = {}
+    for q, out in outs.items():
+        if not isinstance(out, dict) or not out:
+            raise RuntimeError(f"--dump-outputs: {q} step returned no "
+                               f"columns ({type(out).__name__})")
+        for name, v in out.items():
+            a = np.atleast_1d(np.asarray(v))
+            if a.dtype.kind not in "iufb":
+                raise RuntimeError(f"--dump-outputs: {q}.{name} has "
+                                   f"non-numeric dtype {a.dtype}")
+            key = f"{q}.{name}"
+            if a.dtype.kind in "iu" and a.dtype.itemsize == 8:
+                f = a.astype(np.float64)
+                exact = bool(np.all(np.abs(f) < 2.0 ** 63)) and bool(
+                    np.all(f.astype(a.dtype) == a))
+                if not exact:
+                    bits = np.ascontiguousarray(a).view(np.int64)
+                    arrays[key + ".hi32"] = (bits >> 32).astype(np.float64)
+                    arrays[key + ".lo32"] = (
+                        bits & 0xFFFFFFFF).astype(np.float64)
+                arrays[key] = f
+            elif a.dtype.itemsize <= 2:
+                arrays[key] = a.astype(np.float32)
+            else:
+                arrays[key] = a.astype(np.float64)
+    share = DUMP_BUDGET // max(len(arrays), 1) - 128  # .npy header
+    for key, a in arrays.items():
+        cap = share // a.dtype.itemsize
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(
+                a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(outdir / f"{key}.npy", np.ascontiguousarray(a))
+    log(f"dumped {len(arrays)} output arrays to {outdir}")
+
+
 def bench_query(B, q):
     args = B.args
     su = SETUPS[q](B)
-    elapsed, hot_ms = B.time_steps(su["step"])
+    elapsed, hot_ms, last_out = B.time_steps(su["step"])
     n_rows = su["n_rows"]
     total_rows = B.total_rows(n_rows)
     ms_per_step = elapsed / args.steps * 1000.0
@@ -478,7 +536,7 @@ def bench_query(B, q):
             "traffic": traffic_for(q, mode, args.sf),
         }
         cpu = None
-        if not args.skip_cpu_baseline and B.n_gpus == 1:
+        if args.full and not args.skip_cpu_baseline and B.n_gpus == 1:
             rps, nsamp = su["baseline"](B.orc)
             cpu = {
                 "value": rps,
@@ -514,7 +572,7 @@ def bench_query(B, q):
             "cpu_baseline": cpu,
         }
     return su, rec, dict(elapsed=elapsed, hot_ms=hot_ms, n_rows=n_rows,
-                         total_rows=total_rows)
+                         total_rows=total_rows, last_out=last_out)
 
 
 def verify(B, q, su):
@@ -580,13 +638,31 @@ def main():
                     default="all")
     ap.add_argument("--sf", type=float, default=100.0)
     ap.add_argument("--mode", choices=["f64", "dec"], default="f64")
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure q5 (with --query all) and the "
+                         "CPU-oracle baselines, print one line per query "
+                         "ahead of the combined line, and allow --verify")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU-oracle baselines out")
     ap.add_argument("--verify", action="store_true",
-                    help="after timing, check full-size results against the "
-                         "CPU oracle (exact decimal + bitwise f64)")
+                    help="with --full: after timing, check full-size results "
+                         "against the CPU oracle (exact decimal + bitwise "
+                         "f64)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of each query "
+                         "returned as DIR/<query>.<column>.npy")
     args = ap.parse_args()
-    args.queries = ["q1", "q3", "q5"] if args.query == "all" \
-        else [args.query]
+    if args.verify and not args.full:
+        ap.error("--verify is part of the full run: add --full")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.query != "all":
+        args.queries = [args.query]
+    else:
+        # the headline names Q1 & Q3; q5 is an extra leg of the full run
+        args.queries = ["q1", "q3", "q5"] if args.full else ["q1", "q3"]
+    # a plain --query all run prints the combined line alone
+    per_query_lines = args.full or args.query != "all"
 
     B = Bench(args)
     per_q = {}
@@ -595,8 +671,12 @@ def main():
         per_q[q] = (rec, stats)
         if args.verify:
             verify(B, q, su)
-        if rec is not None:
+        if rec is not None and per_query_lines:
             print(json.dumps(rec), flush=True)
+
+    if args.dump_outputs and B.rank == 0:
+        dump_outputs(args.dump_outputs,
+                     {q: per_q[q][1]["last_out"] for q in per_q})
 
     # combined headline: the BASELINE metric names "TPC-H SF100 Q1 & Q3" —
     # one combined step = one Q1 pass + one Q3 pass over the HBM-resident
