@@ -14,7 +14,7 @@ without a GPU) but creating any operator requires an AMD gfx950 GPU and
 fails loudly otherwise.
 """
 from .engine import (  # noqa: F401
-    lib, Operator, Page, Varbin, DictVarbin, DeviceVarbin,
+    lib, Operator, Scope, Page, Varbin, DictVarbin, DeviceVarbin,
     PlanFilterProject,
     PlanHashAggSmall,
     PlanHashBuild, PlanLookupJoin, PlanTopN, PlanPartition, PlanGroupBy,
@@ -27,4 +27,4 @@ from .engine import (  # noqa: F401
     OP_FILTER_PROJECT, OP_HASH_AGG_SMALL, OP_HASH_BUILD, OP_LOOKUP_JOIN,
     OP_TOPN, OP_PARTITION, OP_GROUPBY_MULTI,
 )
-from . import pipelines  # noqa: F401
+from . import pipelines, plans  # noqa: F401

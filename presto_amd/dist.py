@@ -100,17 +100,15 @@ def q3_distributed(cust_page, ord_page, li_page, world, rank, device,
     """
     import numpy as np
     import presto_amd as P
+    from . import plans as pl
     from .engine import lib
 
     use_dist = world > 1
 
     # ---- customer set ----
-    fp = P.PlanFilterProject()
-    fp.n_preds = 1
-    fp.preds[0] = P.Pred(cust_page.channel("mktseg"), P.CMP_EQ, 1, 0.0)
-    fp.n_proj = 1
-    fp.proj[0] = P.Proj(P.PROJ_IDENT, cust_page.channel("custkey"), 0, 0)
-    f = P.Operator(P.OP_FILTER_PROJECT, fp)
+    f = P.Operator(P.OP_FILTER_PROJECT, pl.filter_project(
+        [pl.ident(cust_page.channel("custkey"))],
+        preds=[pl.pred(cust_page.channel("mktseg"), P.CMP_EQ, 1)]))
     f.add_input(cust_page)
     raw = f.get_output_raw()
     ck = _col_to_torch(raw.cols[0], raw.n_rows, device)
@@ -121,40 +119,22 @@ def q3_distributed(cust_page, ord_page, li_page, world, rank, device,
         dist.all_reduce(capt, op=dist.ReduceOp.MAX)
         parts = _gather_padded(ck, int(capt.item()), device)
         ck = torch.cat(parts)
-    bp = P.PlanHashBuild()
-    bp.n_preds = 1
-    bp.preds[0] = P.Pred(0, P.CMP_GE, 1, 0.0)  # drop the 0 padding
-    bp.key_col = 0
-    bp.semijoin_table = -1
-    bp.n_payload = 0
     # dense membership flags sized to the global customer cardinality
-    bp.capacity_hint = cust_page.n_rows * world + world
-    bp.key_set_only = 1
-    bp.dense_array = 1
-    b1 = P.Operator(P.OP_HASH_BUILD, bp)
+    b1 = P.Operator(P.OP_HASH_BUILD, pl.flag_set(
+        0, cust_page.n_rows * world + world,
+        preds=[pl.pred(0, P.CMP_GE, 1)]))  # drop the 0 padding
     b1.add_input(P.Page({"custkey": ck}))
     b1.finish()
     set_tbl = b1.table()
 
     def filter_partition_exchange(page, preds, emit_channels):
         """filter -> partition by col0 of the emitted page -> exchange."""
-        fpl = P.PlanFilterProject()
-        fpl.n_preds = len(preds)
-        for i, pr in enumerate(preds):
-            fpl.preds[i] = pr
-        fpl.n_proj = len(emit_channels)
-        for i, ch in enumerate(emit_channels):
-            fpl.proj[i] = P.Proj(P.PROJ_IDENT, ch, 0, 0)
-        fo = P.Operator(P.OP_FILTER_PROJECT, fpl)
+        fo = P.Operator(P.OP_FILTER_PROJECT, pl.filter_project(
+            [pl.ident(ch) for ch in emit_channels], preds=preds))
         fo.add_input(page)
         fraw = fo.get_output_raw()
-        pp = P.PlanPartition()
-        pp.n_partitions = world
-        pp.key_col = 0
-        pp.n_emit = len(emit_channels)
-        for i in range(len(emit_channels)):
-            pp.emit_cols[i] = i
-        po = P.Operator(P.OP_PARTITION, pp)
+        po = P.Operator(P.OP_PARTITION, pl.partition(
+            world, 0, range(len(emit_channels))))
         po.add_input_raw(fraw)
         fo.destroy()
         counts = po.partition_counts(world)
@@ -186,21 +166,15 @@ def q3_distributed(cust_page, ord_page, li_page, world, rank, device,
     # ---- orders ----
     ocols = filter_partition_exchange(
         ord_page,
-        [P.Pred(ord_page.channel("orderdate"), P.CMP_LT, 9204, 0.0)],
+        [pl.pred(ord_page.channel("orderdate"), P.CMP_LT, 9204)],
         [ord_page.channel("orderkey"), ord_page.channel("orderdate"),
          ord_page.channel("custkey")])
-    b2p = P.PlanHashBuild()
-    b2p.n_preds = 0
-    b2p.key_col = 0
-    b2p.semijoin_table = set_tbl
-    b2p.semijoin_col = 2
-    b2p.n_payload = 1
-    b2p.payload_col[0] = 1
-    b2p.capacity_hint = max(int(ocols["c0"].numel()) // 4, 16)
-    b2p.agg_table = 1
-    b2p.bitmap_max_key = okey_bound  # global orderkey range (keys are
-    # hash-partitioned, so every rank sees global-range keys); 0 = off
-    b2 = P.Operator(P.OP_HASH_BUILD, b2p)
+    b2 = P.Operator(P.OP_HASH_BUILD, pl.hash_build(
+        0, semijoin_table=set_tbl, semijoin_col=2, payload=[1],
+        capacity_hint=max(int(ocols["c0"].numel()) // 4, 16), agg_table=1,
+        # global orderkey range (keys are hash-partitioned, so every rank
+        # sees global-range keys); 0 = off
+        bitmap_max_key=okey_bound))
     b2.add_input(P.Page({k: v for k, v in ocols.items()}))
     b2.finish()
     tbl = b2.table()
@@ -208,26 +182,16 @@ def q3_distributed(cust_page, ord_page, li_page, world, rank, device,
     # ---- lineitem probe ----
     lcols = filter_partition_exchange(
         li_page,
-        [P.Pred(li_page.channel("shipdate"), P.CMP_GT, 9204, 0.0)],
+        [pl.pred(li_page.channel("shipdate"), P.CMP_GT, 9204)],
         [li_page.channel("orderkey"), li_page.channel("extendedprice"),
          li_page.channel("discount")])
-    jp = P.PlanLookupJoin()
-    jp.table = tbl
-    jp.n_preds = 0
-    jp.key_col = 0
-    jp.mode = 1
-    jp.proj = P.Proj(P.PROJ_DISC_PRICE, 1, 2, 0)
-    jp.dec_scale = 4
-    j = P.Operator(P.OP_LOOKUP_JOIN, jp)
+    j = P.Operator(P.OP_LOOKUP_JOIN,
+                   pl.agg_join(tbl, 0, pl.disc_price(1, 2), 4))
     j.add_input(P.Page({k: v for k, v in lcols.items()}))
     j.finish()
     groups = j.get_output_raw()
-    tp = P.PlanTopN()
-    tp.limit = limit
-    tp.val_col = 2 if mode == "dec" else 3
-    tp.date_col = 1
-    tp.key_col = 0
-    t = P.Operator(P.OP_TOPN, tp)
+    t = P.Operator(P.OP_TOPN,
+                   pl.top_n(limit, 2 if mode == "dec" else 3, 1, 0))
     t.add_input_raw(groups)
     t.finish()
     out = t.get_output(["orderkey", "rev", "orderdate"])
@@ -288,6 +252,7 @@ def q5_distributed(cust_page, ord_page, supp_page, li_page, world, rank,
     world == 1 runs the same graph with collectives as identities."""
     import numpy as np
     import presto_amd as P
+    from . import plans as pl
     from .engine import lib
     from .pipelines import Q5Pipeline
 
@@ -328,14 +293,8 @@ def q5_distributed(cust_page, ord_page, supp_page, li_page, world, rank,
     def dense_table(vals):
         n = vals.numel()
         keys = torch.arange(1, n + 1, dtype=torch.int64, device=device)
-        bp = P.PlanHashBuild()
-        bp.key_col = 0
-        bp.semijoin_table = -1
-        bp.n_payload = 1
-        bp.payload_col[0] = 1
-        bp.capacity_hint = n
-        bp.dense_array = 1
-        b = P.Operator(P.OP_HASH_BUILD, bp)
+        b = P.Operator(P.OP_HASH_BUILD, pl.hash_build(
+            0, payload=[1], capacity_hint=n, dense_array=1))
         b.add_input(P.Page({"k": keys, "v": vals}))
         b.finish()
         return b
@@ -343,27 +302,18 @@ def q5_distributed(cust_page, ord_page, supp_page, li_page, world, rank,
     bs = dense_table(snat)
 
     # orders: filter (date) -> partition by orderkey -> exchange
-    fp = P.PlanFilterProject()
-    fp.n_preds = 2
-    fp.preds[0] = P.Pred(ord_page.channel("orderdate"), P.CMP_GE,
-                         Q5Pipeline.Q5_LO, 0.0)
-    fp.preds[1] = P.Pred(ord_page.channel("orderdate"), P.CMP_LT,
-                         Q5Pipeline.Q5_HI, 0.0)
-    fp.n_proj = 2
-    fp.proj[0] = P.Proj(P.PROJ_IDENT, ord_page.channel("orderkey"), 0, 0)
-    fp.proj[1] = P.Proj(P.PROJ_IDENT, ord_page.channel("custkey"), 0, 0)
-    fo = P.Operator(P.OP_FILTER_PROJECT, fp)
+    odate = ord_page.channel("orderdate")
+    fo = P.Operator(P.OP_FILTER_PROJECT, pl.filter_project(
+        [pl.ident(ord_page.channel("orderkey")),
+         pl.ident(ord_page.channel("custkey"))],
+        preds=[pl.pred(odate, P.CMP_GE, Q5Pipeline.Q5_LO),
+               pl.pred(odate, P.CMP_LT, Q5Pipeline.Q5_HI)]))
     fo.add_input(ord_page)
     fraw = fo.get_output_raw()
 
     def partition_exchange_raw(raw, ncols):
-        pp = P.PlanPartition()
-        pp.n_partitions = world
-        pp.key_col = 0
-        pp.n_emit = ncols
-        for i in range(ncols):
-            pp.emit_cols[i] = i
-        po = P.Operator(P.OP_PARTITION, pp)
+        po = P.Operator(P.OP_PARTITION,
+                        pl.partition(world, 0, range(ncols)))
         po.add_input_raw(raw)
         counts = po.partition_counts(world)
         pages = [po.get_output_raw() for _ in range(world)]
@@ -392,17 +342,11 @@ def q5_distributed(cust_page, ord_page, supp_page, li_page, world, rank,
     ocols = partition_exchange_raw(fraw, 2)
     fo.destroy()
 
-    b2p = P.PlanHashBuild()
-    b2p.key_col = 0
-    b2p.semijoin_table = -1
-    b2p.n_payload = 1
-    b2p.payload_col[0] = 0
-    b2p.payload_lookup_table = bc.table()
-    b2p.payload_lookup_key_col = 1
-    b2p.capacity_hint = max(int(ocols["c0"].numel()) + 64, 64)
-    b2p.agg_table = 1
-    b2p.bitmap_max_key = okey_bound
-    b2 = P.Operator(P.OP_HASH_BUILD, b2p)
+    b2 = P.Operator(P.OP_HASH_BUILD, pl.hash_build(
+        0, payload=[0], payload_lookup_table=bc.table(),
+        payload_lookup_key_col=1,
+        capacity_hint=max(int(ocols["c0"].numel()) + 64, 64), agg_table=1,
+        bitmap_max_key=okey_bound))
     b2.add_input(P.Page(ocols))
     b2.finish()
 
@@ -415,18 +359,9 @@ def q5_distributed(cust_page, ord_page, supp_page, li_page, world, rank,
     lraw = lp.to_c()
     lcols = partition_exchange_raw(lraw, 4)
 
-    jp = P.PlanLookupJoin()
-    jp.table = b2.table()
-    jp.key_col = 0
-    jp.mode = 2
-    jp.proj = P.Proj(P.PROJ_DISC_PRICE, 2, 3, 0)
-    jp.dec_scale = 4
-    jp.table2 = bs.table()
-    jp.table2_key_col = 1
-    jp.n_group_vals = len(Q5Pipeline.ASIA)
-    for i, v in enumerate(Q5Pipeline.ASIA):
-        jp.group_vals[i] = v
-    j = P.Operator(P.OP_LOOKUP_JOIN, jp)
+    j = P.Operator(P.OP_LOOKUP_JOIN, pl.lookup_join(
+        b2.table(), 0, 2, proj=pl.disc_price(2, 3), dec_scale=4,
+        table2=bs.table(), table2_key_col=1, group_vals=Q5Pipeline.ASIA))
     j.add_input(P.Page(lcols))
     j.finish()
     out = j.get_output(["nationkey", "rev_lo", "rev_f64", "count"])

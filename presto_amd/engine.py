@@ -3,6 +3,7 @@
 Mirrors include/presto_gpu.h exactly; see that header for the contract and
 the reference citations.
 """
+import contextlib
 import ctypes as C
 import pathlib
 
@@ -345,6 +346,13 @@ class Operator:
         L = lib()
         L.check(L.c.pg_op_add_input(self.h, C.byref(cpage)), "add_input")
 
+    def feed(self, page):
+        """add_input of a Page, or of another operator's raw PgPage."""
+        if isinstance(page, PgPage):
+            self.add_input_raw(page)
+        else:
+            self.add_input(page)
+
     def get_output(self, names=None):
         """Returns dict of numpy arrays, or None. (Materializes device
         outputs to host for harness use; device-to-device chaining uses
@@ -401,3 +409,75 @@ class Operator:
                 self.h = None
         except Exception:
             pass
+
+
+class Scope:
+    """Owns the operators and hash tables of one query (or one long-lived
+    pipeline object).  Leaving the scope — normally or by exception —
+    destroys whatever is still alive in reverse order of creation, so a
+    probe always goes before the table it points at.  release() frees
+    intermediates early (their buffers go back to the size-bucketed pool
+    for the next operator); releasing or closing twice is harmless."""
+
+    def __init__(self):
+        self._live = []  # [operator, table handle or None], creation order
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @contextlib.contextmanager
+    def on_error(self):
+        """For an owner that outlives the block (a pipeline's __init__):
+        close only if the block raises."""
+        try:
+            yield self
+        except BaseException:
+            self.close()
+            raise
+
+    def op(self, kind, plan):
+        op = Operator(kind, plan)
+        self._live.append([op, None])
+        return op
+
+    def pipe(self, kind, plan, page):
+        """Streaming operator over one page (Page, or another operator's
+        raw PgPage): returns (operator, its raw output page)."""
+        op = self.op(kind, plan)
+        op.feed(page)
+        return op, op.get_output_raw()
+
+    def run(self, kind, plan, *pages):
+        """Accumulating operator: feed the pages and finish."""
+        op = self.op(kind, plan)
+        for pg in pages:
+            op.feed(pg)
+        op.finish()
+        return op
+
+    def build(self, plan, *pages):
+        """HASH_BUILD over the pages; its table is recorded (and owned)
+        once the build has finished."""
+        b = self.run(OP_HASH_BUILD, plan, *pages)
+        self._live[-1][1] = b.table()
+        return b
+
+    def _free_table(self, handle):
+        lib().c.pg_table_destroy(handle)
+
+    def release(self, *ops):
+        for op in ops:
+            for i, (o, tbl) in enumerate(self._live):
+                if o is op:
+                    del self._live[i]
+                    if tbl is not None:
+                        self._free_table(tbl)
+                    op.destroy()
+                    break
+
+    def close(self):
+        while self._live:
+            self.release(self._live[-1][0])

@@ -1,0 +1,236 @@
+"""Plan constructors: the one place that fills the ctypes plan structs of
+engine.py (the mirrors of include/presto_gpu.h).
+
+Pure ctypes — no GPU, no .so, importing loads nothing.  Every constructor
+takes sequences (preds=, payload=, emit=, proj=, aggs=), derives the n_*
+counts from them and rejects a sequence longer than the struct's array
+with a ValueError naming the field.  Any other struct field is a plain
+keyword argument passed through (a sequence for an array field); an
+unknown name is a TypeError.
+"""
+import ctypes as C
+
+from .engine import (
+    Pred, Proj, Agg, PlanFilterProject, PlanHashAggSmall, PlanHashBuild,
+    PlanLookupJoin, PlanGroupBy, PlanTopN, PlanPartition,
+    CMP_CONTAINS2, CMP_NOT_CONTAINS2,
+    PROJ_IDENT, PROJ_DISC_PRICE, PROJ_CHARGE, PROJ_MUL, PROJ_DIV,
+    PROJ_KEYSHL, PROJ_SUBDIV, PROJ_KEYSHL_DIV,
+    AGG_COUNT, AGG_SUM_F64, AGG_SUM_DEC, AGG_SUM_I64,
+)
+
+
+# ---- predicates ----
+def pred(col, op, val):
+    """col <op> literal: an int compares as ival, a float as dval."""
+    if isinstance(val, float):
+        return Pred(col, op, 0, val)
+    return Pred(col, op, int(val), 0.0)
+
+
+def pred_cols(col, op, rhs, plus=0):
+    """col <op> channel rhs (+ integer constant `plus`); rhs_col is stored
+    biased by one so that 0 keeps meaning "literal compare"."""
+    p = Pred(col, op, plus, 0.0)
+    p.rhs_col = rhs + 1
+    return p
+
+
+def pred_varbin(col, op, needle, needle2=None):
+    """VARBIN CONTAINS / PREFIX of `needle`; the ordered two-needle
+    CONTAINS2 / NOT_CONTAINS2 stores both concatenated in sval, slen = the
+    length of the FIRST and ival = the length of the second."""
+    if (needle2 is not None) != (op in (CMP_CONTAINS2, CMP_NOT_CONTAINS2)):
+        raise ValueError("needle2 goes with CONTAINS2 / NOT_CONTAINS2 only")
+    sval = needle + (needle2 or b"")
+    if len(sval) > Pred.sval.size:
+        raise ValueError(f"sval: {len(sval)} bytes exceed {Pred.sval.size}")
+    p = Pred(col, op, len(needle2 or b""), 0.0)
+    p.sval = sval
+    p.slen = len(needle)
+    return p
+
+
+# ---- projections ----
+def ident(ch):
+    return Proj(PROJ_IDENT, ch, 0, 0)
+
+
+def disc_price(ep, dc):
+    return Proj(PROJ_DISC_PRICE, ep, dc, 0)
+
+
+def charge(ep, dc, tx):
+    return Proj(PROJ_CHARGE, ep, dc, tx)
+
+
+def mul(a, b):
+    return Proj(PROJ_MUL, a, b, 0)
+
+
+def div(a, b):
+    return Proj(PROJ_DIV, a, b, 0)
+
+
+def keyshl(a, b, shift):
+    return Proj(PROJ_KEYSHL, a, b, shift)
+
+
+def subdiv(a, b, c):
+    return Proj(PROJ_SUBDIV, a, b, c)
+
+
+def keyshl_div(a, b, shift, divisor):
+    return Proj(PROJ_KEYSHL_DIV, a, b, (shift << 16) | divisor)
+
+
+# ---- aggregates ----
+def count():
+    return Agg(AGG_COUNT, ident(0), 0)
+
+
+def sum_dec(proj, scale):
+    return Agg(AGG_SUM_DEC, proj, scale)
+
+
+def sum_f64(proj, scale=0):
+    return Agg(AGG_SUM_F64, proj, scale)
+
+
+def sum_i64(proj):
+    return Agg(AGG_SUM_I64, proj, 0)
+
+
+# ---- struct filling ----
+def _fill(arr, field, seq):
+    """Copy seq into the ctypes array of struct field `field`; returns
+    the count for the field's n_* companion."""
+    seq = list(seq)
+    if len(seq) > len(arr):
+        raise ValueError(f"{field}: {len(seq)} entries exceed the struct's "
+                         f"{len(arr)}")
+    for i, v in enumerate(seq):
+        arr[i] = v
+    return len(seq)
+
+
+_ARRAY_FIELDS = {
+    cls: {name: issubclass(tp, C.Array) for name, tp in cls._fields_}
+    for cls in (PlanFilterProject, PlanHashAggSmall, PlanHashBuild,
+                PlanLookupJoin)}
+
+
+def _set(plan, fields):
+    """The pass-through keyword arguments; the n_* counts are derived."""
+    is_array = _ARRAY_FIELDS[type(plan)]
+    for name, value in fields.items():
+        if name not in is_array or name.startswith("n_"):
+            raise TypeError(f"{type(plan).__name__} has no settable field "
+                            f"{name!r}")
+        if is_array[name]:
+            _fill(getattr(plan, name), name, value)
+        else:
+            setattr(plan, name, value)
+    return plan
+
+
+def _aggs(plan, preds, filters, aggs):
+    """preds + filters share preds[]: only preds[0..n_preds) filter rows,
+    the rest are per-aggregate FILTER predicates.  An aggregate is an Agg
+    (unfiltered) or (Agg, i) gated by filters[i]."""
+    preds, filters = list(preds), list(filters)
+    _fill(plan.preds, "preds", preds + filters)
+    plan.n_preds = len(preds)
+    pairs = [a if isinstance(a, tuple) else (a, None) for a in aggs]
+    if any(f is not None and not 0 <= f < len(filters) for _, f in pairs):
+        raise ValueError("agg_filter: index outside filters=")
+    plan.n_aggs = _fill(plan.aggs, "aggs", [a for a, _ in pairs])
+    _fill(plan.agg_filter, "agg_filter",
+          [-1 if f is None else len(preds) + f for _, f in pairs])
+
+
+# ---- one constructor per operator kind ----
+def hash_build(key_col=0, *, preds=(), payload=(), semijoin_table=-1,
+               **fields):
+    p = PlanHashBuild()
+    p.n_preds = _fill(p.preds, "preds", preds)
+    p.key_col = key_col
+    p.n_payload = _fill(p.payload_col, "payload_col", payload)
+    p.semijoin_table = semijoin_table
+    return _set(p, fields)
+
+
+def flag_set(key_col, capacity_hint, preds=()):
+    """Dense key flag set: 1-byte membership flags over keys 1..hint."""
+    return hash_build(key_col, preds=preds, capacity_hint=capacity_hint,
+                      key_set_only=1, dense_array=1)
+
+
+def range_group(capacity_hint):
+    """Range-group table: the group domain is the key range 1..hint
+    itself (no build input, no hash)."""
+    return hash_build(capacity_hint=capacity_hint, range_group=1)
+
+
+def lookup_join(table, key_col, mode, *, preds=(), filters=(), emit=(),
+                aggs=(), group_vals=(), **fields):
+    """mode 0 emits `emit` probe channels + the payloads; mode 1 is the
+    fused grouped aggregate (single proj=/dec_scale=, or aggs= with
+    optional filters= and acc_pack fields); modes 2/3 take table2= etc."""
+    p = PlanLookupJoin()
+    p.table = table
+    p.key_col = key_col
+    p.mode = mode
+    _aggs(p, preds, filters, aggs)
+    p.n_emit = _fill(p.emit_probe_cols, "emit_probe_cols", emit)
+    p.n_group_vals = _fill(p.group_vals, "group_vals", group_vals)
+    return _set(p, fields)
+
+
+def emit_join(table, key_col, emit, preds=()):
+    return lookup_join(table, key_col, 0, preds=preds, emit=emit)
+
+
+def agg_join(table, key_col, proj, dec_scale=0, preds=(), **fields):
+    """Single fused grouped SUM of `proj` per matched key (mode 1)."""
+    return lookup_join(table, key_col, 1, preds=preds, proj=proj,
+                       dec_scale=dec_scale, **fields)
+
+
+def small_agg(aggs, *, preds=(), keys=(), **fields):
+    """keys: up to two (channel, listed key values) pairs."""
+    p = PlanHashAggSmall()
+    p.n_preds = _fill(p.preds, "preds", preds)
+    p.n_aggs = _fill(p.aggs, "aggs", aggs)
+    keys = list(keys)
+    p.n_keys = _fill(p.key_col, "key_col", [c for c, _ in keys])
+    for i, (_, vals) in enumerate(keys):
+        p.n_vals[i] = _fill(p.key_vals[i], "key_vals", vals)
+    return _set(p, fields)
+
+
+def filter_project(proj, *, preds=(), **fields):
+    p = PlanFilterProject()
+    p.n_preds = _fill(p.preds, "preds", preds)
+    p.n_proj = _fill(p.proj, "proj", proj)
+    return _set(p, fields)
+
+
+def group_by(keys, aggs, capacity_hint, *, preds=(), filters=()):
+    p = PlanGroupBy()
+    p.n_keys = _fill(p.key_col, "key_col", keys)
+    p.capacity_hint = capacity_hint
+    _aggs(p, preds, filters, aggs)
+    return p
+
+
+def top_n(limit, val_col, date_col, key_col):
+    return PlanTopN(limit, val_col, date_col, key_col)
+
+
+def partition(n_partitions, key_col, emit):
+    p = PlanPartition()
+    p.n_partitions = n_partitions
+    p.key_col = key_col
+    p.n_emit = _fill(p.emit_cols, "emit_cols", emit)
+    return p

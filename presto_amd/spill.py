@@ -12,11 +12,10 @@ Partition count: ceil(total_bytes / budget_bytes) rounded up — with 288 GB
 of HBM3E per GPU a single partition covers every TPC-H size this repo
 benches, so the tests force small budgets to exercise the path.
 """
+from . import plans as pl
 from .engine import (
-    Operator, Page, PlanHashBuild, PlanLookupJoin, PlanTopN, PlanPartition,
-    Pred, Proj, lib,
-    OP_HASH_BUILD, OP_LOOKUP_JOIN, OP_TOPN, OP_PARTITION,
-    CMP_LT, CMP_GT, CMP_EQ, PROJ_DISC_PRICE,
+    Page, Scope, OP_LOOKUP_JOIN, OP_TOPN, OP_PARTITION,
+    CMP_LT, CMP_GT, CMP_EQ,
 )
 
 
@@ -24,20 +23,13 @@ def spill_partition(page: Page, key: str, n_parts: int):
     """Split a page into n_parts host-resident pages by bigint key hash
     (PartitionedOutputOperator.partitionPage math).  The d2h copy is the
     'spill'; partitions return as host Pages ready to re-stage."""
-    pp = PlanPartition()
-    pp.n_partitions = n_parts
-    pp.key_col = page.channel(key)
-    pp.n_emit = len(page.names)
-    for i in range(len(page.names)):
-        pp.emit_cols[i] = i
-    op = Operator(OP_PARTITION, pp)
-    op.add_input(page)
-    parts = []
-    for _ in range(n_parts):
-        cols = op.get_output(list(page.names))  # d2h: the spill
-        parts.append(Page(cols))
-    op.destroy()
-    return parts
+    with Scope() as s:
+        op = s.op(OP_PARTITION, pl.partition(
+            n_parts, page.channel(key), range(len(page.names))))
+        op.add_input(page)
+        # d2h: the spill
+        return [Page(op.get_output(list(page.names)))
+                for _ in range(n_parts)]
 
 
 def q3_grace(cust: Page, orders: Page, li: Page, n_parts: int, mode="dec",
@@ -50,71 +42,39 @@ def q3_grace(cust: Page, orders: Page, li: Page, n_parts: int, mode="dec",
     are identical to the resident pipeline bit for bit."""
     from .pipelines import Q3_DATE
 
-    b1p = PlanHashBuild()
-    b1p.n_preds = 1
-    b1p.preds[0] = Pred(cust.channel("mktseg"), CMP_EQ, 1, 0.0)
-    b1p.key_col = cust.channel("custkey")
-    b1p.semijoin_table = -1
-    b1p.capacity_hint = cust.n_rows
-    b1p.key_set_only = 1
-    b1p.dense_array = 1
-    b1 = Operator(OP_HASH_BUILD, b1p)
-    b1.add_input(cust)
-    b1.finish()
-
-    o_parts = spill_partition(orders, "orderkey", n_parts)
-    l_parts = spill_partition(li, "orderkey", n_parts)
-
     rows = []
-    for op_page, lp_page in zip(o_parts, l_parts):
-        b2p = PlanHashBuild()
-        b2p.n_preds = 1
-        b2p.preds[0] = Pred(op_page.channel("orderdate"), CMP_LT, Q3_DATE,
-                            0.0)
-        b2p.key_col = op_page.channel("orderkey")
-        b2p.semijoin_table = b1.table()
-        b2p.semijoin_col = op_page.channel("custkey")
-        b2p.n_payload = 1
-        b2p.payload_col[0] = op_page.channel("orderdate")
-        b2p.capacity_hint = max(op_page.n_rows // 4, 16)
-        b2p.agg_table = 1
-        b2 = Operator(OP_HASH_BUILD, b2p)
-        b2.add_input(op_page)
-        b2.finish()
+    with Scope() as s:
+        b1 = s.build(pl.flag_set(
+            cust.channel("custkey"), cust.n_rows,
+            preds=[pl.pred(cust.channel("mktseg"), CMP_EQ, 1)]), cust)
 
-        jp = PlanLookupJoin()
-        jp.table = b2.table()
-        jp.n_preds = 1
-        jp.preds[0] = Pred(lp_page.channel("shipdate"), CMP_GT, Q3_DATE, 0.0)
-        jp.key_col = lp_page.channel("orderkey")
-        jp.mode = 1
-        jp.proj = Proj(PROJ_DISC_PRICE, lp_page.channel("extendedprice"),
-                       lp_page.channel("discount"), 0)
-        jp.dec_scale = 4
-        j = Operator(OP_LOOKUP_JOIN, jp)
-        j.add_input(lp_page)
-        j.finish()
-        groups = j.get_output_raw()
+        o_parts = spill_partition(orders, "orderkey", n_parts)
+        l_parts = spill_partition(li, "orderkey", n_parts)
 
-        tp = PlanTopN()
-        tp.limit = limit
-        tp.val_col = 2 if mode == "dec" else 3
-        tp.date_col = 1
-        tp.key_col = 0
-        t = Operator(OP_TOPN, tp)
-        t.add_input_raw(groups)
-        t.finish()
-        out = t.get_output(["orderkey", "revenue", "orderdate"])
-        for i in range(len(out["orderkey"])):
-            rows.append((int(out["orderkey"][i]), int(out["revenue"][i])
-                         if mode == "dec" else float(out["revenue"][i]),
-                         int(out["orderdate"][i])))
-        t.destroy()
-        j.destroy()
-        lib().c.pg_table_destroy(b2.table())
-        b2.destroy()
-
-    lib().c.pg_table_destroy(b1.table())
-    b1.destroy()
+        for op_page, lp_page in zip(o_parts, l_parts):
+            b2 = s.build(pl.hash_build(
+                op_page.channel("orderkey"),
+                preds=[pl.pred(op_page.channel("orderdate"), CMP_LT,
+                               Q3_DATE)],
+                semijoin_table=b1.table(),
+                semijoin_col=op_page.channel("custkey"),
+                payload=[op_page.channel("orderdate")],
+                capacity_hint=max(op_page.n_rows // 4, 16), agg_table=1),
+                op_page)
+            j = s.run(OP_LOOKUP_JOIN, pl.agg_join(
+                b2.table(), lp_page.channel("orderkey"),
+                pl.disc_price(lp_page.channel("extendedprice"),
+                              lp_page.channel("discount")), 4,
+                preds=[pl.pred(lp_page.channel("shipdate"), CMP_GT,
+                               Q3_DATE)]), lp_page)
+            t = s.run(OP_TOPN,
+                      pl.top_n(limit, 2 if mode == "dec" else 3, 1, 0),
+                      j.get_output_raw())
+            out = t.get_output(["orderkey", "revenue", "orderdate"])
+            for i in range(len(out["orderkey"])):
+                rows.append((int(out["orderkey"][i]), int(out["revenue"][i])
+                             if mode == "dec" else float(out["revenue"][i]),
+                             int(out["orderdate"][i])))
+            s.release(t, j, b2)
     rows.sort(key=lambda r: (-r[1], r[2], r[0]))
     return rows[:limit]

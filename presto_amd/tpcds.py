@@ -19,13 +19,10 @@ import ctypes as C
 
 import numpy as np
 
+from . import plans as pl
 from .engine import (
-    Operator, Page, PlanFilterProject, PlanHashBuild, PlanLookupJoin,
-    PlanGroupBy, Pred, Proj, Agg,
-    OP_FILTER_PROJECT, OP_HASH_BUILD, OP_LOOKUP_JOIN, OP_GROUPBY_MULTI,
+    Scope, OP_FILTER_PROJECT, OP_LOOKUP_JOIN, OP_GROUPBY_MULTI,
     CMP_LT, CMP_GT, CMP_GE, CMP_LE, CMP_EQ, CMP_NE,
-    PROJ_IDENT, PROJ_MUL, PROJ_KEYSHL, PROJ_SUBDIV, PROJ_KEYSHL_DIV,
-    AGG_COUNT, AGG_SUM_I64, lib,
 )
 
 DATE_COUNT = 73049
@@ -164,73 +161,37 @@ class DsGen:
                 tuple(int(x[i]) for x in b) for i in range(n)]
 
 
-def _filter(page, preds=(), projs=(), semi=None, semi_col=0, raw=False):
-    fp = PlanFilterProject()
-    fp.n_preds = len(preds)
-    for i, p in enumerate(preds):
-        fp.preds[i] = p
-    fp.n_proj = len(projs)
-    for i, p in enumerate(projs):
-        fp.proj[i] = p
-    if semi is not None:
-        fp.semijoin_table = semi
-        fp.semijoin_col = semi_col
-    else:
-        fp.semijoin_table = 0
-    f = Operator(OP_FILTER_PROJECT, fp)
-    if raw:
-        f.add_input_raw(page)
-    else:
-        f.add_input(page)
-    return f, f.get_output_raw()
+def _filter(s, page, preds=(), projs=(), semi=0, semi_col=0):
+    """Filter/project (+ optional semijoin) over a Page or raw page:
+    returns (operator, raw output page)."""
+    return s.pipe(OP_FILTER_PROJECT, pl.filter_project(
+        projs, preds=preds, semijoin_table=semi, semijoin_col=semi_col),
+        page)
 
 
-def _date_set(date_page, lo, hi):
-    """Dense key set of date_sks whose qname/year column c1 is in
-    [lo, hi] — the dynamic-filter analog of the date_dim dimension
-    joins."""
-    f, out = _filter(date_page,
-                     preds=(Pred(1, CMP_GE, lo, 0.0),
-                            Pred(1, CMP_LE, hi, 0.0)),
-                     projs=(Proj(PROJ_IDENT, 0, 0, 0),))
-    bp = PlanHashBuild()
-    bp.key_col = 0
-    bp.semijoin_table = -1
-    bp.capacity_hint = DATE_COUNT + 1
-    bp.key_set_only = 1
-    bp.dense_array = 1
-    b = Operator(OP_HASH_BUILD, bp)
-    b.add_input_raw(out)
-    b.finish()
-    f.destroy()
+def _dense_set(s, page, preds, cap):
+    """Dense key set of the column-0 sks passing preds — the
+    dynamic-filter analog of a dimension join."""
+    f, out = _filter(s, page, preds=preds, projs=[pl.ident(0)])
+    b = s.build(pl.flag_set(0, cap + 1), out)
+    s.release(f)
     return b
 
 
-def _chain_build(page_raw, key_col, payload_cols, hint):
-    bp = PlanHashBuild()
-    bp.key_col = key_col
-    bp.semijoin_table = -1
-    bp.n_payload = len(payload_cols)
-    for i, c in enumerate(payload_cols):
-        bp.payload_col[i] = c
-    bp.capacity_hint = max(hint, 16)
-    b = Operator(OP_HASH_BUILD, bp)
-    b.add_input_raw(page_raw)
-    b.finish()
-    return b
+def _date_set(s, date_page, lo, hi):
+    """date_sks whose qname/year column c1 is in [lo, hi]."""
+    return _dense_set(s, date_page, [pl.pred(1, CMP_GE, lo),
+                                     pl.pred(1, CMP_LE, hi)], DATE_COUNT)
 
 
-def _emit_join(page_raw, table, key_col, emit_cols):
-    jp = PlanLookupJoin()
-    jp.table = table
-    jp.key_col = key_col
-    jp.mode = 0
-    jp.n_emit = len(emit_cols)
-    for i, c in enumerate(emit_cols):
-        jp.emit_probe_cols[i] = c
-    j = Operator(OP_LOOKUP_JOIN, jp)
-    j.add_input_raw(page_raw)
-    return j, j.get_output_raw()
+def _chain_build(s, page_raw, key_col, payload_cols, hint):
+    return s.build(pl.hash_build(key_col, payload=payload_cols,
+                                 capacity_hint=max(hint, 16)), page_raw)
+
+
+def _emit_join(s, page_raw, table, key_col, emit_cols):
+    return s.pipe(OP_LOOKUP_JOIN, pl.emit_join(table, key_col, emit_cols),
+                  page_raw)
 
 
 def ds_q17(gen, sf, ss_page, sr_page, cs_page, date_page, q0):
@@ -240,84 +201,59 @@ def ds_q17(gen, sf, ss_page, sr_page, cs_page, date_page, q0):
     count/sum/sum-of-squares of the three quantities, integer-exact.
     Returns host rows [(item_id, state, c,s,q x3)] sorted, after the
     display-side item_id/state fold."""
-    ops, tables = [], []
+    with Scope() as s:
+        set_q0 = _date_set(s, date_page, q0, q0)
+        set_q02 = _date_set(s, date_page, q0, q0 + 2)
 
-    set_q0 = _date_set(date_page, q0, q0)
-    set_q02 = _date_set(date_page, q0, q0 + 2)
-    tables += [set_q0, set_q02]
+        # store_sales in q0 -> chained table keyed by ticket
+        f_ss, p_ss = _filter(s, ss_page,
+                             projs=(pl.ident(4),   # ticket
+                                    pl.ident(2),   # cust
+                                    pl.ident(1),   # item
+                                    pl.ident(5),   # qty
+                                    pl.ident(3)),  # store
+                             semi=set_q0.table())
+        b1 = _chain_build(s, p_ss, 0, (1, 2, 3, 4), p_ss.n_rows)
 
-    # store_sales in q0 -> chained table keyed by ticket
-    f_ss = _filter(ss_page,
-                   projs=(Proj(PROJ_IDENT, 4, 0, 0),   # ticket
-                          Proj(PROJ_IDENT, 2, 0, 0),   # cust
-                          Proj(PROJ_IDENT, 1, 0, 0),   # item
-                          Proj(PROJ_IDENT, 5, 0, 0),   # qty
-                          Proj(PROJ_IDENT, 3, 0, 0)),  # store
-                   semi=set_q0.table(), semi_col=0)
-    ops.append(f_ss[0])
-    b1 = _chain_build(f_ss[1], 0, (1, 2, 3, 4), f_ss[1].n_rows)
-    tables.append(b1)
+        # store_returns in q0..q0+2 probe on ticket, then (cust,item)
+        # equality
+        f_sr, p_sr = _filter(s, sr_page,
+                             projs=(pl.ident(3),   # ticket
+                                    pl.ident(2),   # cust
+                                    pl.ident(1),   # item
+                                    pl.ident(4)),  # rqty
+                             semi=set_q02.table())
+        j1, p1 = _emit_join(s, p_sr, b1.table(), 0, (1, 2, 3))
+        # p1: [r_cust, r_item, rqty, s_cust, s_item, s_qty, s_store]
+        f_eq, p_eq = _filter(s, p1,
+                             preds=(pl.pred_cols(0, CMP_EQ, 3),
+                                    pl.pred_cols(1, CMP_EQ, 4)),
+                             projs=(pl.keyshl(0, 1, 20),  # (cust<<20)|item
+                                    pl.ident(5),          # ssqty
+                                    pl.ident(2),          # rqty
+                                    pl.ident(6),          # store
+                                    pl.ident(1)))         # item
+        b2 = _chain_build(s, p_eq, 0, (1, 2, 3, 4), p_eq.n_rows)
 
-    # store_returns in q0..q0+2 probe on ticket, then (cust,item) equality
-    f_sr = _filter(sr_page,
-                   projs=(Proj(PROJ_IDENT, 3, 0, 0),   # ticket
-                          Proj(PROJ_IDENT, 2, 0, 0),   # cust
-                          Proj(PROJ_IDENT, 1, 0, 0),   # item
-                          Proj(PROJ_IDENT, 4, 0, 0)),  # rqty
-                   semi=set_q02.table(), semi_col=0)
-    ops.append(f_sr[0])
-    j1, p1 = _emit_join(f_sr[1], b1.table(), 0, (1, 2, 3))
-    ops.append(j1)
-    # p1: [r_cust, r_item, rqty, s_cust, s_item, s_qty, s_store]
-    eq1 = Pred(0, CMP_EQ, 0, 0.0)
-    eq1.rhs_col = 3 + 1
-    eq2 = Pred(1, CMP_EQ, 0, 0.0)
-    eq2.rhs_col = 4 + 1
-    f_eq = _filter(p1, preds=(eq1, eq2),
-                   projs=(Proj(PROJ_KEYSHL, 0, 1, 20),  # (cust<<20)|item
-                          Proj(PROJ_IDENT, 5, 0, 0),    # ssqty
-                          Proj(PROJ_IDENT, 2, 0, 0),    # rqty
-                          Proj(PROJ_IDENT, 6, 0, 0),    # store
-                          Proj(PROJ_IDENT, 1, 0, 0)),   # item
-                   raw=True)
-    ops.append(f_eq[0])
-    b2 = _chain_build(f_eq[1], 0, (1, 2, 3, 4), f_eq[1].n_rows)
-    tables.append(b2)
+        # catalog re-purchases in q0..q0+2 probe on (cust, item)
+        f_cs, p_cs = _filter(s, cs_page,
+                             projs=(pl.keyshl(2, 1, 20),
+                                    pl.ident(3)),   # csqty
+                             semi=set_q02.table())
+        j2, p2 = _emit_join(s, p_cs, b2.table(), 0, (1,))
+        # p2: [csqty, ssqty, rqty, store, item]
 
-    # catalog re-purchases in q0..q0+2 probe on (cust, item)
-    f_cs = _filter(cs_page,
-                   projs=(Proj(PROJ_KEYSHL, 2, 1, 20),
-                          Proj(PROJ_IDENT, 3, 0, 0)),   # csqty
-                   semi=set_q02.table(), semi_col=0)
-    ops.append(f_cs[0])
-    j2, p2 = _emit_join(f_cs[1], b2.table(), 0, (1,))
-    ops.append(j2)
-    # p2: [csqty, ssqty, rqty, store, item]
-
-    g = PlanGroupBy()
-    g.n_keys = 2
-    g.key_col[0] = 4  # item
-    g.key_col[1] = 3  # store
-    g.capacity_hint = max(p2.n_rows * 2, 4096)
-    g.n_aggs = 6
-    specs = ((1, False), (1, True), (2, False), (2, True), (0, False),
-             (0, True))
-    for i, (ch, sq) in enumerate(specs):
-        g.aggs[i] = Agg(AGG_SUM_I64,
-                        Proj(PROJ_MUL, ch, ch, 0) if sq
-                        else Proj(PROJ_IDENT, ch, 0, 0), 0)
-        g.agg_filter[i] = -1
-    gop = Operator(OP_GROUPBY_MULTI, g)
-    gop.add_input_raw(p2)
-    gop.finish()
-    out = gop.get_output(["item", "store", "s_ss", "q_ss", "s_sr", "q_sr",
-                          "s_cs", "q_cs", "cnt"])
-    gop.destroy()
-    for o in ops:
-        o.destroy()
-    for t in tables:
-        lib().c.pg_table_destroy(t.table())
-        t.destroy()
+        # per quantity channel: its sum, then its sum of squares
+        gop = s.run(OP_GROUPBY_MULTI, pl.group_by(
+            [4, 3],  # item, store
+            [pl.sum_i64(pl.mul(ch, ch) if sq else pl.ident(ch))
+             for ch in (1, 2, 0) for sq in (False, True)],
+            max(p2.n_rows * 2, 4096)), p2)
+        out = gop.get_output(["item", "store", "s_ss", "q_ss", "s_sr",
+                              "q_sr", "s_cs", "q_cs", "cnt"])
+        # fixed end-of-query order (see pipelines.py): streams, then tables
+        s.release(gop, f_ss, f_sr, j1, f_eq, f_cs, j2,
+                  set_q0, set_q02, b1, b2)
 
     # display-side fold: item_sk -> i_item_id (pairs share an id),
     # store_sk -> s_state; equal (id, state) groups merge
@@ -345,174 +281,94 @@ def ds_q72(gen, sf, cs_page, inv_pages, cr_page, date_page, cdemo_page,
     LEFT JOINs to promotion (promo/no_promo split) and catalog_returns
     (row multiplicity).  Grouped by (item, warehouse, week_seq).
     Returns host rows [(item_id, wh, week, no_promo, promo, total)]."""
-    ops, tables = [], []
+    # the promo / no_promo split as per-aggregate FILTERs on channel 3
+    promo_split = [pl.pred(3, CMP_EQ, 0), pl.pred(3, CMP_NE, 0)]
+    with Scope() as s:
+        set_year = _date_set(s, date_page, year, year)
+        # demographics dynamic-filter sets (dense sks)
+        cdset = _dense_set(s, cdemo_page, [pl.pred(1, CMP_EQ, marital)],
+                           1920800)
+        hdset = _dense_set(s, hdemo_page, [pl.pred(1, CMP_EQ, buypot)],
+                           7200)
 
-    set_year = _date_set(date_page, year, year)
-    tables.append(set_year)
+        # cs: year + ship > sold + 5 + demographics, then (item, week) key
+        # cs_page cols: [sold, ship, item, order, qty, cdemo, hdemo, promo]
+        f1, p = _filter(s, cs_page,
+                        preds=[pl.pred_cols(1, CMP_GT, 0, plus=5)],
+                        projs=[pl.ident(c) for c in (0, 2, 3, 4, 5, 6, 7)],
+                        semi=set_year.table())
+        # [sold, item, order, qty, cdemo, hdemo, promo]
+        f2, p = _filter(s, p,
+                        projs=[pl.ident(c) for c in (0, 1, 2, 3, 5, 6)],
+                        semi=cdset.table(), semi_col=4)
+        # [sold, item, order, qty, hdemo, promo]
+        f3, p = _filter(s, p, projs=(pl.subdiv(0, 0, 7),  # week
+                                     pl.ident(1), pl.ident(2), pl.ident(3),
+                                     pl.ident(5)),
+                        semi=hdset.table(), semi_col=4)
+        # [week, item, order, qty, promo]
+        f4, p = _filter(s, p, projs=(pl.keyshl(1, 0, 14),   # item<<14|wk
+                                     pl.ident(3),           # qty
+                                     pl.ident(4),           # promo
+                                     pl.keyshl(1, 2, 25)))  # crkey
+        b3 = _chain_build(s, p, 0, (1, 2, 3), p.n_rows)
 
-    # demographics dynamic-filter sets (dense sks)
-    def demo_set(page, code, cap):
-        f, out = _filter(page, preds=(Pred(1, CMP_EQ, code, 0.0),),
-                         projs=(Proj(PROJ_IDENT, 0, 0, 0),))
-        bp = PlanHashBuild()
-        bp.key_col = 0
-        bp.semijoin_table = -1
-        bp.capacity_hint = cap + 1
-        bp.key_set_only = 1
-        bp.dense_array = 1
-        b = Operator(OP_HASH_BUILD, bp)
-        b.add_input_raw(out)
-        b.finish()
-        f.destroy()
-        return b
+        # inventory probes the (item, week) table; on-hand < ordered.
+        # ONE pass: the (item<<14 | date/7) key and the week channel are
+        # both derived in the same projection set (KEYSHL_DIV / SUBDIV)
+        joined, fqs = [], []
+        for inv in inv_pages:
+            fi, pi = _filter(s, inv, projs=(pl.keyshl_div(1, 0, 14, 7),
+                                            pl.ident(1),
+                                            pl.subdiv(0, 0, 7),
+                                            pl.ident(2), pl.ident(3)))
+            jj, pj = _emit_join(s, pi, b3.table(), 0, (1, 2, 3, 4))
+            s.release(fi)
+            # pj: [item, wk, wh, qoh, qty, promo, crkey]
+            fq, pq = _filter(s, pj, preds=[pl.pred_cols(3, CMP_LT, 4)],
+                             projs=[pl.ident(c) for c in (0, 1, 2, 5, 6)])
+            s.release(jj)
+            fqs.append(fq)
+            joined.append(pq)  # [item, wk, wh, promo, crkey]
 
-    cdset = demo_set(cdemo_page, marital, 1920800)
-    hdset = demo_set(hdemo_page, buypot, 7200)
-    tables += [cdset, hdset]
+        # base counts per (item, wk, wh) with the promo split
+        gop1 = s.run(OP_GROUPBY_MULTI, pl.group_by(
+            range(3), [(pl.count(), 0), (pl.count(), 1)],
+            max(sum(pq.n_rows for pq in joined) * 2, 4096),
+            filters=promo_split), *joined)
+        base = gop1.get_output(["item", "wk", "wh", "no_promo", "promo",
+                                "cnt"])
+        s.release(gop1)
 
-    # cs: year + ship > sold + 5 + demographics, then (item, week) key
-    ship_pred = Pred(1, CMP_GT, 5, 0.0)  # ship > sold + 5
-    ship_pred.rhs_col = 0 + 1
-    f1 = _filter(cs_page, preds=(ship_pred,),
-                 projs=tuple(Proj(PROJ_IDENT, c, 0, 0)
-                             for c in (0, 2, 3, 4, 5, 6, 7)),
-                 semi=set_year.table(), semi_col=0)
-    ops.append(f1[0])
-    # f1: [sold, item, cust?, ...] -> cs_page cols are
-    # [sold, ship, item, order, qty, cdemo, hdemo, promo]
-    # emitted: [sold, item, order, qty, cdemo, hdemo, promo]
-    f2 = _filter(f1[1], projs=tuple(Proj(PROJ_IDENT, c, 0, 0)
-                                    for c in (0, 1, 2, 3, 5, 6)),
-                 semi=cdset.table(), semi_col=4, raw=True)
-    ops.append(f2[0])
-    # [sold, item, order, qty, hdemo, promo]
-    f3 = _filter(f2[1], projs=(Proj(PROJ_SUBDIV, 0, 0, 7),  # week
-                               Proj(PROJ_IDENT, 1, 0, 0),
-                               Proj(PROJ_IDENT, 2, 0, 0),
-                               Proj(PROJ_IDENT, 3, 0, 0),
-                               Proj(PROJ_IDENT, 5, 0, 0)),
-                 semi=hdset.table(), semi_col=4, raw=True)
-    ops.append(f3[0])
-    # [week, item, order, qty, promo]
-    f4 = _filter(f3[1], projs=(Proj(PROJ_KEYSHL, 1, 0, 14),  # item<<14|wk
-                               Proj(PROJ_IDENT, 3, 0, 0),    # qty
-                               Proj(PROJ_IDENT, 4, 0, 0),    # promo
-                               Proj(PROJ_KEYSHL, 1, 2, 25)),  # crkey
-                 raw=True)
-    ops.append(f4[0])
-    b3 = _chain_build(f4[1], 0, (1, 2, 3), f4[1].n_rows)
-    tables.append(b3)
+        # catalog_returns multiplicity: LEFT JOIN row expansion =
+        # base + (matches - 1) for matched rows
+        f_cr, p_cr = _filter(s, cr_page, projs=(pl.keyshl(0, 1, 25),))
+        gopc = s.run(OP_GROUPBY_MULTI, pl.group_by(
+            [0], [pl.count()], max(p_cr.n_rows, 1024)), p_cr)
+        crg = gopc.get_output_raw()  # [crkey, cnt, cnt]
+        ocr = s.build(pl.hash_build(0, payload=[1],
+                                    capacity_hint=max(crg.n_rows, 16),
+                                    agg_table=1), crg)
+        s.release(gopc)
 
-    # inventory probes the (item, week) table; on-hand < ordered.
-    # ONE pass: the (item<<14 | date/7) key and the week channel are both
-    # derived in the same projection set (KEYSHL_DIV / SUBDIV)
-    joined_parts = []
-    for inv in inv_pages:
-        fi2 = _filter(inv,
-                      projs=(Proj(PROJ_KEYSHL_DIV, 1, 0, (14 << 16) | 7),
-                             Proj(PROJ_IDENT, 1, 0, 0),
-                             Proj(PROJ_SUBDIV, 0, 0, 7),
-                             Proj(PROJ_IDENT, 2, 0, 0),
-                             Proj(PROJ_IDENT, 3, 0, 0)))
-        jj, pj = _emit_join(fi2[1], b3.table(), 0, (1, 2, 3, 4))
-        fi2[0].destroy()
-        # pj: [item, wk, wh, qoh, qty, promo, crkey]
-        qlt = Pred(3, CMP_LT, 0, 0.0)
-        qlt.rhs_col = 4 + 1
-        fq = _filter(pj, preds=(qlt,),
-                     projs=tuple(Proj(PROJ_IDENT, c, 0, 0)
-                                 for c in (0, 1, 2, 5, 6)), raw=True)
-        jj.destroy()
-        joined_parts.append(fq)
-        # fq out: [item, wk, wh, promo, crkey]
-
-    # base counts per (item, wk, wh) with the promo split
-    g1 = PlanGroupBy()
-    g1.n_keys = 3
-    for i in range(3):
-        g1.key_col[i] = i
-    g1.capacity_hint = max(sum(f[1].n_rows for f in joined_parts) * 2,
-                           4096)
-    g1.n_preds = 0
-    g1.preds[0] = Pred(3, CMP_EQ, 0, 0.0)
-    g1.preds[1] = Pred(3, CMP_NE, 0, 0.0)
-    g1.n_aggs = 2
-    g1.aggs[0] = Agg(AGG_COUNT, Proj(PROJ_IDENT, 0, 0, 0), 0)
-    g1.aggs[1] = Agg(AGG_COUNT, Proj(PROJ_IDENT, 0, 0, 0), 0)
-    g1.agg_filter[0] = 0
-    g1.agg_filter[1] = 1
-    gop1 = Operator(OP_GROUPBY_MULTI, g1)
-    for f in joined_parts:
-        gop1.add_input_raw(f[1])
-    gop1.finish()
-    base = gop1.get_output(["item", "wk", "wh", "no_promo", "promo",
-                            "cnt"])
-    gop1.destroy()
-
-    # catalog_returns multiplicity: LEFT JOIN row expansion =
-    # base + (matches - 1) for matched rows
-    f_cr = _filter(cr_page, projs=(Proj(PROJ_KEYSHL, 0, 1, 25),))
-    ops.append(f_cr[0])
-    gcr = PlanGroupBy()
-    gcr.n_keys = 1
-    gcr.key_col[0] = 0
-    gcr.capacity_hint = max(f_cr[1].n_rows, 1024)
-    gcr.n_aggs = 1
-    gcr.aggs[0] = Agg(AGG_COUNT, Proj(PROJ_IDENT, 0, 0, 0), 0)
-    gcr.agg_filter[0] = -1
-    gopc = Operator(OP_GROUPBY_MULTI, gcr)
-    gopc.add_input_raw(f_cr[1])
-    gopc.finish()
-    crg = gopc.get_output_raw()  # [crkey, cnt, cnt]
-
-    bcr = PlanHashBuild()
-    bcr.key_col = 0
-    bcr.semijoin_table = -1
-    bcr.n_payload = 1
-    bcr.payload_col[0] = 1
-    bcr.capacity_hint = max(crg.n_rows, 16)
-    bcr.agg_table = 1
-    ocr = Operator(OP_HASH_BUILD, bcr)
-    ocr.add_input_raw(crg)
-    ocr.finish()
-    gopc.destroy()
-    tables.append(ocr)
-
-    g2 = PlanGroupBy()
-    g2.n_keys = 3
-    for i in range(3):
-        g2.key_col[i] = i
-    g2.capacity_hint = max(len(base["item"]) * 2, 4096)
-    g2.n_preds = 0
-    g2.preds[0] = Pred(3, CMP_EQ, 0, 0.0)
-    g2.preds[1] = Pred(3, CMP_NE, 0, 0.0)
-    g2.n_aggs = 3
-    g2.aggs[0] = Agg(AGG_SUM_I64, Proj(PROJ_SUBDIV, 4, 1, 1), 0)
-    g2.aggs[1] = Agg(AGG_SUM_I64, Proj(PROJ_SUBDIV, 4, 1, 1), 0)
-    g2.aggs[2] = Agg(AGG_SUM_I64, Proj(PROJ_SUBDIV, 4, 1, 1), 0)
-    g2.agg_filter[0] = 0
-    g2.agg_filter[1] = 1
-    g2.agg_filter[2] = -1
-    gop2 = Operator(OP_GROUPBY_MULTI, g2)
-    any_extra = False
-    for f in joined_parts:
-        jm, pm = _emit_join(f[1], ocr.table(), 4, (0, 1, 2, 3))
-        # pm: [item, wk, wh, promo, cr_cnt]
-        if pm.n_rows:
-            gop2.add_input_raw(pm)
-            any_extra = True
-        jm.destroy()
-    gop2.finish()
-    extra = gop2.get_output(["item", "wk", "wh", "e_np", "e_p", "e_t",
-                             "cnt"]) if any_extra else None
-    gop2.destroy()
-    for f in joined_parts:
-        f[0].destroy()
-    for o in ops:
-        o.destroy()
-    for t in tables:
-        lib().c.pg_table_destroy(t.table())
-        t.destroy()
+        extra_rows = pl.sum_i64(pl.subdiv(4, 1, 1))  # cr_cnt - 1
+        gop2 = s.op(OP_GROUPBY_MULTI, pl.group_by(
+            range(3), [(extra_rows, 0), (extra_rows, 1), extra_rows],
+            max(len(base["item"]) * 2, 4096), filters=promo_split))
+        any_extra = False
+        for pq in joined:
+            jm, pm = _emit_join(s, pq, ocr.table(), 4, (0, 1, 2, 3))
+            # pm: [item, wk, wh, promo, cr_cnt]
+            if pm.n_rows:
+                gop2.add_input_raw(pm)
+                any_extra = True
+            s.release(jm)
+        gop2.finish()
+        extra = gop2.get_output(["item", "wk", "wh", "e_np", "e_p", "e_t",
+                                 "cnt"]) if any_extra else None
+        # fixed end-of-query order (see pipelines.py): streams, then tables
+        s.release(gop2, *fqs, f1, f2, f3, f4, f_cr,
+                  set_year, cdset, hdset, b3, ocr)
 
     # host fold (display side), vectorized: item_sk -> item_id, merge
     # base + extra group rows, sort by (item_id, wh, week)

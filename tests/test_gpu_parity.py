@@ -2290,3 +2290,21 @@ def test_q9_composite_flow_repro(P):
     for o in (og, ops_):
         lib().c.pg_table_destroy(o.table())
         o.destroy()
+
+
+def test_scope_unwinds_on_plan_error(P):
+    """A plan-validation error part-way through a query frees what was
+    built so far: probing a key-set-only table is rejected by
+    pg_op_create, and once the Scope has unwound the table is gone."""
+    from presto_amd import plans as pl
+    from presto_amd.engine import Scope
+    keys = P.Page({"k": np.arange(1, 17, dtype=np.int64)})
+    with pytest.raises(RuntimeError, match="cannot probe a key-set-only"):
+        with Scope() as s:
+            b = s.build(pl.hash_build(0, capacity_hint=16, key_set_only=1),
+                        keys)
+            handle = b.table()
+            s.op(P.OP_LOOKUP_JOIN, pl.emit_join(handle, 0, [0]))
+    L = P.lib()
+    assert L.c.pg_table_reset_acc(handle) != 0
+    assert "table not found" in L.err()
