@@ -62,6 +62,10 @@ double pg_last_hot_kernel_ms(void);
  * launches per step: the max is the dominant one) */
 double pg_hot_max_ms(void);
 void pg_hot_reset(void);
+/* how many HASH_AGG_SMALL pages this process has sent to the specialized
+ * Q1-shape kernel rather than the generic one (tests pin which plans
+ * take it) */
+int64_t pg_q1_fast_launches(void);
 
 /* ---- Page / Block descriptors (SURVEY.md §8b struct) ----
  * Concrete layouts follow the Java blocks: fixed-width values array +
@@ -92,7 +96,14 @@ typedef struct {
     int32_t tag;            /* pg_type */
     int32_t on_device;      /* 1: data is a device pointer */
     void* data;             /* values array (VARBIN: the byte buffer) */
-    const uint8_t* null_mask; /* optional, 1 byte/pos, 1 = null; may be NULL */
+    const uint8_t* null_mask; /* optional, 1 byte/pos, 1 = null; may be NULL.
+                                 Within operators it is honored by
+                                 predicates: a null on either side of a
+                                 comparison excludes the row; projections
+                                 and aggregate inputs read the values
+                                 array as is.  pg_page_serialize /
+                                 pg_page_deserialize carry masks through
+                                 (nulls-as-bits on the wire). */
     const int32_t* offsets; /* VARBIN only: offsets (n_rows+1, or dict_n+1
                                for dictionary columns) */
     /* dictionary encoding (DictionaryBlock.java:60-86): when dict_ids is
@@ -181,7 +192,22 @@ typedef struct {
 typedef enum {
     PG_AGG_COUNT = 0,    /* CountAggregation.java:34 */
     PG_AGG_SUM_F64 = 1,  /* DoubleSumAggregation (deterministic schedule,
-                            DESIGN.md §determinism) */
+                            DESIGN.md §determinism).  DOMAIN in
+                            GROUPBY_MULTI and the fused-agg probes
+                            (LOOKUP_JOIN modes 1/3), which sum in exact
+                            64.64 fixed point: every addend must satisfy
+                            0 <= x < 2^53 with no fraction bits below
+                            2^-64 (x = 0 or x >= ~2^-12); the result is
+                            then the correctly rounded exact sum.  A
+                            negative, NaN, >= 2^53 or finer addend makes
+                            finish fail with an error naming SUM_F64
+                            (signed f64 sums are unsupported there).
+                            NOT checked: LOOKUP_JOIN mode 2, whose
+                            callers guarantee non-negative money (its
+                            kernels are off the benchmark headline, so
+                            the cost of a check there is unmeasured).
+                            HASH_AGG_SMALL sums plain f64 in its fixed
+                            schedule and has no such domain. */
     PG_AGG_SUM_DEC = 2,  /* exact decimal ticks; scale from dec_scale
                             (hive-decimal semantics of the golden vectors) */
     PG_AGG_SUM_I64 = 3,  /* LongSumAggregation.java:33-37 */
@@ -193,7 +219,19 @@ typedef enum {
 typedef struct {
     int32_t func;     /* pg_agg_func */
     pg_proj proj;     /* input expression */
-    int32_t dec_scale; /* for SUM_DEC: ticks = round(value * 10^dec_scale) */
+    int32_t dec_scale; /* for SUM_DEC: ticks = round(value * 10^dec_scale).
+                          Rounding is half away from zero, so negative
+                          values mirror positive ones (-1.23 at scale 2
+                          -> -123 ticks, -0.01 -> -1); the
+                          operands of MUL/DISC_PRICE/CHARGE are each
+                          rounded to hundredths the same way.
+                          EXCEPTIONS, defined for non-negative money
+                          only: the Q1-shape fast path of HASH_AGG_SMALL
+                          (Q1 plan shape over f64 columns without null
+                          masks) and the Q5-shape mode-2 probe
+                          (DISC_PRICE over f64 columns on a packed
+                          table, no predicates) round with a plain
+                          +0.5. */
 } pg_agg;
 
 /* -------- operator kinds + plans -------- */
@@ -446,7 +484,8 @@ typedef struct {
 } pg_plan_groupby;
 
 typedef struct {
-    /* ORDER BY value DESC, date ASC, key ASC LIMIT n  (Q3 shape) */
+    /* ORDER BY value DESC, date ASC, key ASC LIMIT n  (Q3 shape).
+     * NaN values are unsupported (their order is unspecified). */
     int32_t limit;
     int32_t val_col;  /* i64 (decimal ticks) or f64 */
     int32_t date_col; /* i32 */

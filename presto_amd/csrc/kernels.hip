@@ -157,6 +157,8 @@ static void hot_end()
 extern "C" double pg_last_hot_kernel_ms(void) { return g_last_hot_ms; }
 extern "C" double pg_hot_max_ms(void) { return g_hot_max_ms; }
 extern "C" void pg_hot_reset(void) { g_hot_max_ms = 0.0; }
+static int64_t g_q1_fast_launches = 0;
+extern "C" int64_t pg_q1_fast_launches(void) { return g_q1_fast_launches; }
 
 /* ------------------------------------------------------------------ */
 /* device helpers                                                     */
@@ -335,8 +337,38 @@ __device__ inline double d_eval_proj_f64(const pg_page& pg, const pg_proj& p,
     return v * (1.0 + c);
 }
 
+/* scaled value -> integer ticks, rounding half away from zero (the
+ * header's ticks = round(value * 10^dec_scale)).  Non-negative x takes
+ * the (i64)(x + 0.5) of the oracle unchanged; a plain +0.5 would truncate
+ * negative values toward zero (-1.23 -> -122). */
+__device__ inline int64_t d_round_ticks(double x)
+{
+    return (int64_t)(x + (x < 0 ? -0.5 : 0.5));
+}
+
+/* checked entry to the 64.64 accumulators: fx128_from_f64 is exact only for
+ * 0 <= p < 2^53 whose fraction fits 64 bits (fixed128.h).  Anything else
+ * (negative, NaN, >= 2^53, fraction bits below 2^-64) contributes nothing
+ * and bumps *bad, which the host raises as a SUM_F64 domain error. */
+__device__ inline void d_fx128_from_f64_ck(double p, uint64_t* hi,
+                                           uint64_t* lo,
+                                           unsigned long long* bad)
+{
+    bool ok = p >= 0.0 && p < 9007199254740992.0; /* false for NaN */
+    if (ok) {
+        fx128_from_f64(p, hi, lo);
+        double frac = p - (double)*hi;
+        ok = (double)*lo == frac * 18446744073709551616.0;
+    }
+    if (!ok) {
+        *hi = 0;
+        *lo = 0;
+        atomicAdd(bad, 1ull);
+    }
+}
+
 /* exact decimal ticks; operand-wise decomposition identical to the oracle
- * (oracle.c): cents = (i64)(x*100+0.5) etc. */
+ * (oracle.c) on its non-negative domain: cents = (i64)(x*100+0.5) etc. */
 __device__ inline int64_t d_eval_proj_dec(const pg_page& pg, const pg_agg& ag,
                                           int64_t i)
 {
@@ -349,7 +381,7 @@ __device__ inline int64_t d_eval_proj_dec(const pg_page& pg, const pg_agg& ag,
         double a = d_load_f64(c, i);
         double s = 1.0;
         for (int k = 0; k < ag.dec_scale; k++) s *= 10.0;
-        return (int64_t)(a * s + 0.5);
+        return d_round_ticks(a * s);
     }
     if (p.kind == PG_PROJ_SUBDIV)
         return (d_load_i64(pg.cols[p.a], i) - (int64_t)p.b) /
@@ -359,12 +391,12 @@ __device__ inline int64_t d_eval_proj_dec(const pg_page& pg, const pg_agg& ag,
         /* raw integer product (e.g. Q21's exact sum of squared
          * suppkeys) — scale-4 money products keep the cents path */
         return d_load_i64(pg.cols[p.a], i) * d_load_i64(pg.cols[p.b], i);
-    int64_t cents = (int64_t)(d_load_f64(pg.cols[p.a], i) * 100.0 + 0.5);
-    int64_t d = (int64_t)(d_load_f64(pg.cols[p.b], i) * 100.0 + 0.5);
+    int64_t cents = d_round_ticks(d_load_f64(pg.cols[p.a], i) * 100.0);
+    int64_t d = d_round_ticks(d_load_f64(pg.cols[p.b], i) * 100.0);
     if (p.kind == PG_PROJ_MUL) return cents * d; /* scale 4 ticks */
     int64_t v = cents * (100 - d);
     if (p.kind == PG_PROJ_DISC_PRICE) return v;
-    int64_t t = (int64_t)(d_load_f64(pg.cols[p.c], i) * 100.0 + 0.5);
+    int64_t t = d_round_ticks(d_load_f64(pg.cols[p.c], i) * 100.0);
     return v * (100 + t);
 }
 
@@ -658,8 +690,11 @@ __global__ __launch_bounds__(FT_NTHREADS) void k_agg_q1(
             q2.x = qty[base]; e2.x = ep[base]; d2.x = dc[base];
             t2.x = tx[base]; s2.x = sd[base];
             r0 = rf[base]; l0 = ls[base];
-            q2.y = 0; e2.y = 0; d2.y = 0; t2.y = 0; s2.y = 0x7fffffff;
-            r1 = k00; l1 = k10;
+            /* no second row: sel is false for it below (!pair), whatever
+             * the predicate constant; the zeros only keep the registers
+             * defined */
+            q2.y = 0; e2.y = 0; d2.y = 0; t2.y = 0; s2.y = 0;
+            r1 = 0; l1 = 0;
         }
 #pragma unroll
         for (int r = 0; r < 2; r++) {
@@ -667,7 +702,7 @@ __global__ __launch_bounds__(FT_NTHREADS) void k_agg_q1(
             double d = r ? d2.y : d2.x, t = r ? t2.y : t2.x;
             int32_t sdv = r ? s2.y : s2.x;
             uint8_t rv = r ? r1 : r0, lv = r ? l1 : l0;
-            bool sel = sdv <= ship_max;
+            bool sel = sdv <= ship_max && (r == 0 || pair);
             int i0 = rv == k00 ? 0 : (rv == k01 ? 1 : (rv == k02 ? 2 : -1));
             int i1 = lv == k10 ? 0 : (lv == k11 ? 1 : -1);
             if (i0 < 0 || i1 < 0) {
@@ -1769,7 +1804,8 @@ __global__ __launch_bounds__(256) void k_probe_agg(
     pg_page pg, pg_plan_lookup_join plan, const int64_t* keys,
     const uint8_t* tags, int64_t mask, int64_t lmask, int32_t pbits,
     const unsigned long long* kbits, int64_t bmax,
-    unsigned long long* acc, int32_t aw, unsigned long long* ovf)
+    unsigned long long* acc, int32_t aw,
+    unsigned long long* ovf /* [tick overflow, SUM_F64 domain] */)
 {
     /* 4 CONSECUTIVE rows per thread with run dedup: neighboring rows
      * often share the join key (lineitem is clustered by orderkey), so
@@ -1836,7 +1872,7 @@ __global__ __launch_bounds__(256) void k_probe_agg(
             if (!plan.dec_only && !plan.dec_min) {
                 double p = d_eval_proj_f64(pg, plan.proj, i);
                 uint64_t phi, plo;
-                fx128_from_f64(p, &phi, &plo);
+                d_fx128_from_f64_ck(p, &phi, &plo, ovf + 1);
                 uint64_t nlo = run_flo + plo;
                 run_fhi += phi + (nlo < plo ? 1u : 0u);
                 run_flo = nlo;
@@ -1932,22 +1968,21 @@ __global__ __launch_bounds__(256) void k_probe_agg_q3(
             int64_t sl = slot[j];
             if (sl < 0) continue;
             double e = ep[base + j], d = dc[base + j];
-            int64_t cents = (int64_t)(e * 100.0 + 0.5);
-            int64_t di = (int64_t)(d * 100.0 + 0.5);
+            int64_t cents = d_round_ticks(e * 100.0);
+            int64_t di = d_round_ticks(d * 100.0);
             int64_t ticks = cents * (100 - di);
             /* no per-add overflow round trip here: this specialization is
              * gated on the DISC_PRICE money shape (dec_scale 4, f64 money
              * columns < 1e7), so |ticks| < 1e9 per row and an int64 slot
              * sum cannot wrap before ~9.2e9 matched rows on ONE key —
              * far beyond a page.  The generic k_probe_agg keeps the
-             * checked add. */
-            (void)ovf;
+             * checked add.  ovf[1] counts SUM_F64 domain errors. */
             unsigned long long* s = acc + (size_t)sl * aw;
             atomicAdd(&s[0], (unsigned long long)ticks);
             if (!dec_only) {
                 double pr = e * (1.0 - d);
                 uint64_t phi, plo;
-                fx128_from_f64(pr, &phi, &plo);
+                d_fx128_from_f64_ck(pr, &phi, &plo, ovf + 1);
                 unsigned long long old = atomicAdd(&s[1], plo);
                 atomicAdd(&s[2], phi + (old > ~plo ? 1ull : 0ull));
             }
@@ -1993,7 +2028,7 @@ __global__ __launch_bounds__(256) void k_probe_agg_pay(
         if (!plan.dec_only) {
             double p = d_eval_proj_f64(pg, plan.proj, i);
             uint64_t phi, plo;
-            fx128_from_f64(p, &phi, &plo);
+            d_fx128_from_f64_ck(p, &phi, &plo, ovf + 1);
             unsigned long long old = atomicAdd(&s[1], plo);
             atomicAdd(&s[2], phi + (old > ~plo ? 1ull : 0ull));
         }
@@ -2624,7 +2659,8 @@ __device__ inline int64_t d_gb_key(const pg_page& pg, int32_t col,
 __global__ __launch_bounds__(256) void k_groupby_multi(
     pg_page pg, pg_plan_groupby plan, unsigned int* state, int64_t* kv,
     int64_t cap, int64_t mask, unsigned long long* acc, int32_t acc_words,
-    gb_agg_off offs, unsigned long long* counters /* [ovf, full] */)
+    gb_agg_off offs,
+    unsigned long long* counters /* [ovf, full, groups, SUM_F64 domain] */)
 {
     const int n_keys = plan.n_keys;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2702,7 +2738,7 @@ __global__ __launch_bounds__(256) void k_groupby_multi(
                 case PG_AGG_SUM_F64: {
                     double v = d_eval_proj_f64(pg, plan.aggs[a].proj, i);
                     uint64_t phi, plo;
-                    fx128_from_f64(v, &phi, &plo);
+                    d_fx128_from_f64_ck(v, &phi, &plo, counters + 3);
                     unsigned long long old = atomicAdd(w, plo);
                     atomicAdd(w + 1, phi + (old > ~plo ? 1ull : 0ull));
                     break;
@@ -3475,7 +3511,9 @@ static SelResult sel_count(const pg_page& pg,
     DevBuf d_counts;
     d_counts.alloc(FLT_NB * sizeof(int64_t));
     auto selbits = std::make_shared<DevBuf>();
-    selbits->alloc(((size_t)pg.n_rows / 64 + 2) * 8);
+    /* k_sel_emit reads the mask word of all four waves of every 256-row
+     * window it enters, the last (partial) one included */
+    selbits->alloc(((size_t)(pg.n_rows + 255) / 256 * 4 + 1) * 8);
     hipLaunchKernelGGL(k_sel_count, dim3(FLT_NB), dim3(256), 0, g_stream, pg,
                        plan, chunk, (int64_t*)d_counts.p, set_ptr(semi),
                        set_mask_of(semi), semi_col,
@@ -3709,12 +3747,22 @@ struct AggSmallOp : Op {
             p.preds[0].op != PG_CMP_LE || p.preds[0].rhs_col != 0)
             return false;
         const pg_agg* a = p.aggs;
-        if (!(a[0].func != PG_AGG_COUNT && a[0].proj.kind == PG_PROJ_IDENT &&
+        if (!(a[0].proj.kind == PG_PROJ_IDENT &&
               a[1].proj.kind == PG_PROJ_IDENT &&
               a[2].proj.kind == PG_PROJ_DISC_PRICE &&
               a[3].proj.kind == PG_PROJ_CHARGE &&
               a[4].proj.kind == PG_PROJ_IDENT && a[5].func == PG_AGG_COUNT))
             return false;
+        /* the kernel computes five SUMs and a count: MIN/MAX (or a
+         * count) in a sum slot takes the generic kernel */
+        for (int i = 0; i < 5; i++) {
+            int32_t fn = a[i].func;
+            if (dec ? !(fn == PG_AGG_SUM_DEC || fn == PG_AGG_SUM_I64)
+                    : fn != PG_AGG_SUM_F64)
+                return false;
+        }
+        /* it always reports unlisted keys and never reads a null mask */
+        if (p.drop_unlisted_keys) return false;
         if (a[2].proj.a != a[1].proj.a || a[3].proj.a != a[1].proj.a ||
             a[3].proj.b != a[2].proj.b || a[4].proj.a != a[2].proj.b)
             return false;
@@ -3726,10 +3774,15 @@ struct AggSmallOp : Op {
         for (int i = 0; i < 4; i++) {
             const pg_col& c = pg.cols[chans[i]];
             if (c.tag != PG_T_F64 || ((uintptr_t)c.data & 15)) return false;
+            if (c.null_mask) return false;
         }
         if (((uintptr_t)pg.cols[p.preds[0].col].data & 7)) return false;
         if (pg.cols[p.key_col[0]].tag != PG_T_U8 ||
             pg.cols[p.key_col[1]].tag != PG_T_U8)
+            return false;
+        if (pg.cols[p.preds[0].col].null_mask ||
+            pg.cols[p.key_col[0]].null_mask ||
+            pg.cols[p.key_col[1]].null_mask)
             return false;
         return true;
     }
@@ -3741,6 +3794,7 @@ struct AggSmallOp : Op {
             var = e ? atoi(e) : 1; /* nontemporal default: +17% measured */
         }
         const pg_plan_hash_agg_small& p = plan;
+        g_q1_fast_launches++;
         const double* qty = (const double*)pg.cols[p.aggs[0].proj.a].data;
         const double* ep = (const double*)pg.cols[p.aggs[1].proj.a].data;
         const double* dc = (const double*)pg.cols[p.aggs[2].proj.b].data;
@@ -4468,7 +4522,8 @@ struct JoinOp : Op {
     Table* t = nullptr;
     Table* t2 = nullptr; /* mode 2 dense table */
     DevBuf m2_acc;       /* mode 2: [dec, flo, fhi, cnt] x 8 groups */
-    DevBuf ovf;          /* tick-sum overflow counter (modes 1/3) */
+    DevBuf ovf;          /* modes 1/3: [tick-sum overflow, SUM_F64 addends
+                            outside the 64.64 domain] */
     void init()
     {
         std::lock_guard<std::mutex> lk(g_mu);
@@ -4492,7 +4547,7 @@ struct JoinOp : Op {
         /* mode 0 emit over a slot-payload table: unique keys, payloads
          * indexed by slot (no chains) */
         if (plan.mode == 1 || plan.mode == 3) {
-            ovf.alloc(8);
+            ovf.alloc(16);
             ovf.zero();
         }
         if (plan.mode == 1 && plan.n_aggs > 0) {
@@ -4692,8 +4747,10 @@ struct JoinOp : Op {
             return;
         }
         if (plan.mode == 1) {
-            /* specialized fast path for the Q3 shape */
+            /* specialized fast path for the Q3 shape (a SUM: dec_min
+             * keeps the generic kernel) */
             bool spec = plan.proj.kind == PG_PROJ_DISC_PRICE &&
+                        !plan.dec_min &&
                         sp.pg.cols[plan.key_col].tag == PG_T_I64 &&
                         sp.pg.cols[plan.proj.a].tag == PG_T_F64 &&
                         sp.pg.cols[plan.proj.b].tag == PG_T_F64 &&
@@ -4891,13 +4948,18 @@ struct JoinOp : Op {
         }
         if (plan.mode != 1 && plan.mode != 3) return;
         {
-            unsigned long long h_ovf = 0;
-            CHKV(hipMemcpy(&h_ovf, ovf.p, 8, hipMemcpyDeviceToHost));
-            if (h_ovf)
+            unsigned long long h_ovf[2] = {0, 0};
+            CHKV(hipMemcpy(h_ovf, ovf.p, 16, hipMemcpyDeviceToHost));
+            if (h_ovf[0])
                 throw std::runtime_error(
                     "bigint/decimal SUM overflow in grouped probe "
                     "(Math.addExact semantics, "
                     "LongSumAggregation.java:33-37)");
+            if (h_ovf[1])
+                throw std::runtime_error(
+                    "SUM_F64 addend outside the exact fixed-point domain "
+                    "in grouped probe (needs 0 <= x < 2^53 with no "
+                    "fraction bits below 2^-64)");
         }
         /* extract groups: slots with count>0, slot-ascending (mode 3
          * groups live in table2) */
@@ -5057,7 +5119,8 @@ struct GroupByOp : Op {
         kv.alloc((size_t)cap * 8 * plan.n_keys);
         acc.alloc((size_t)cap * acc_words * 8);
         acc.zero();
-        counters.alloc(24); /* [tick ovf, table full, distinct groups] */
+        counters.alloc(32); /* [tick ovf, table full, distinct groups,
+                               SUM_F64 domain] */
         counters.zero();
         bool mm = false;
         for (int a = 0; a < plan.n_aggs; a++)
@@ -5098,8 +5161,8 @@ struct GroupByOp : Op {
     }
     void finish() override
     {
-        unsigned long long c[3];
-        CHKV(hipMemcpy(c, counters.p, 24, hipMemcpyDeviceToHost));
+        unsigned long long c[4];
+        CHKV(hipMemcpy(c, counters.p, 32, hipMemcpyDeviceToHost));
         if (c[1])
             throw std::runtime_error(
                 "groupby table full: raise capacity_hint");
@@ -5107,6 +5170,11 @@ struct GroupByOp : Op {
             throw std::runtime_error(
                 "bigint/decimal SUM overflow in groupby "
                 "(Math.addExact semantics)");
+        if (c[3])
+            throw std::runtime_error(
+                "SUM_F64 addend outside the exact fixed-point domain in "
+                "groupby (needs 0 <= x < 2^53 with no fraction bits below "
+                "2^-64)");
         int64_t total = (int64_t)c[2]; /* distinct groups, counted at
                                           claim time */
         if (total * 100 > cap * 85)

@@ -176,6 +176,15 @@ class Varbin:
             else np.empty(0, np.uint8)
         self.n = len(strings)
 
+    @classmethod
+    def from_arrays(cls, data, offsets):
+        """Wrap an existing layout: uint8 bytes + int32 offsets (n+1)."""
+        v = cls.__new__(cls)
+        v.data = np.ascontiguousarray(data, np.uint8)
+        v.offsets = np.ascontiguousarray(offsets, np.int32)
+        v.n = len(v.offsets) - 1
+        return v
+
     def __len__(self):
         return self.n
 
@@ -304,9 +313,8 @@ def _read_output_page(cpage, names=None):
                                               nb), "d2h")
                 else:
                     C.memmove(data.ctypes.data, col.data, nb)
-            v = Varbin.__new__(Varbin)
-            v.offsets, v.data, v.n = offs, data, n
-            out[names[i] if names else f"c{i}"] = v
+            out[names[i] if names else f"c{i}"] = Varbin.from_arrays(data,
+                                                                     offs)
             continue
         dt = _TAG_NP[col.tag]
         a = np.empty(n, dt)

@@ -714,6 +714,15 @@ def test_bigint_groupby_sum_via_composition(P, oracle_lib):
     np.add.at(exp_c, pos, 1)
     assert np.array_equal(got_s, exp_s)
     assert np.array_equal(got_c, exp_c)
+    # f64 sums: the exact sum of the f64 products, rounded once (fsum)
+    import math
+    prod = price * (1.0 - disc)
+    by_key = [[] for _ in uniq]
+    for p_, v_ in zip(pos.tolist(), prod.tolist()):
+        by_key[p_].append(v_)
+    exp_f = np.array([math.fsum(v_) for v_ in by_key])
+    assert np.array_equal(out["sum_f64"][order].view(np.int64),
+                          exp_f.view(np.int64))
 
 
 def _varbin_page(P, extra_cols, strings):
@@ -1676,15 +1685,16 @@ def test_groupby_multi_fuzz(P):
 
     # numpy reference (same aggregation semantics, order-free)
     import collections
+    import math
     ref = collections.defaultdict(
-        lambda: [0, 0.0, 0, 2**63 - 1, -2**63, 0])
+        lambda: [0, [], 0, 2**63 - 1, -2**63, 0])
     sel = v_i != 17
     for idx in np.nonzero(sel)[0]:
         key = (int(k_i64[idx]), int(k_i32[idx]), int(k_u8[idx]),
                int(ids[idx]))
         r = ref[key]
         r[0] += int(v_i[idx])
-        r[1] += float(v_f[idx])
+        r[1].append(float(v_f[idx]))
         if flt[idx] == 1:
             r[2] += 1
         r[3] = min(r[3], int(v_i[idx]))
@@ -1702,8 +1712,9 @@ def test_groupby_multi_fuzz(P):
         g = got[key]
         assert g[0] == r[0], (key, g, r)
         # fx128 sum is the correctly-rounded sum of the f64 addends —
-        # compare against numpy's sequential sum within 1 ulp
-        assert abs(g[1] - r[1]) <= abs(r[1]) * 1e-12
+        # bit-equal to math.fsum of the group's values
+        assert np.float64(g[1]).view(np.int64) == \
+            np.float64(math.fsum(r[1])).view(np.int64), (key, g[1])
         assert g[2] == r[2] and g[3] == r[3] and g[4] == r[4]
         assert g[5] == r[5]
 
