@@ -99,11 +99,21 @@ typedef struct {
     const uint8_t* null_mask; /* optional, 1 byte/pos, 1 = null; may be NULL.
                                  Within operators it is honored by
                                  predicates: a null on either side of a
-                                 comparison excludes the row; projections
-                                 and aggregate inputs read the values
-                                 array as is.  pg_page_serialize /
-                                 pg_page_deserialize carry masks through
-                                 (nulls-as-bits on the wire). */
+                                 comparison excludes the row, and
+                                 PG_CMP_IS_NULL / PG_CMP_IS_NOT_NULL test
+                                 the mask itself; projections and
+                                 aggregate inputs read the values array
+                                 as is.  Output pages carry masks only
+                                 out of the outer LOOKUP_JOIN modes
+                                 (PG_JOIN_PROBE_OUTER and up: null-padded
+                                 payloads, gathered probe-column masks,
+                                 the drain page); every other operator
+                                 emits null_mask = NULL.  A mask follows
+                                 its column: host for host columns,
+                                 device for device columns.
+                                 pg_page_serialize / pg_page_deserialize
+                                 carry masks through (nulls-as-bits on
+                                 the wire). */
     const int32_t* offsets; /* VARBIN only: offsets (n_rows+1, or dict_n+1
                                for dictionary columns) */
     /* dictionary encoding (DictionaryBlock.java:60-86): when dict_ids is
@@ -137,7 +147,19 @@ typedef enum { PG_CMP_LT = 0, PG_CMP_LE, PG_CMP_GT, PG_CMP_GE, PG_CMP_EQ,
                 * Q13's o_comment NOT LIKE '%special%requests%'):
                 * sval holds a then b concatenated, slen = len(a),
                 * ival = len(b) */
-               PG_CMP_CONTAINS2, PG_CMP_NOT_CONTAINS2 } pg_cmp;
+               PG_CMP_CONTAINS2, PG_CMP_NOT_CONTAINS2,
+               /* null tests, any column type (VARBIN and dictionary
+                * columns included): they read the column's null_mask
+                * and nothing else — a column without a mask is never
+                * null; ival, dval, sval and rhs_col are ignored.  They
+                * are decided before the "a null excludes the row" rule,
+                * so IS_NULL keeps exactly the rows that rule drops.
+                * As a per-aggregate FILTER, IS_NOT_NULL turns COUNT
+                * into count(col).  Accepted wherever predicates are,
+                * except as build-side filters of dense_array and
+                * agg_table HASH_BUILDs (single-scan kernels that
+                * evaluate comparisons only): those fail pg_op_create. */
+               PG_CMP_IS_NULL, PG_CMP_IS_NOT_NULL } pg_cmp;
 
 typedef struct {
     int32_t col;   /* input channel */
@@ -367,6 +389,13 @@ typedef struct {
     int32_t dense_payload_bias;
 } pg_plan_hash_build;
 
+/* pg_plan_lookup_join.mode values of the emit joins (modes 1-3 are the
+ * fused aggregating probes described in the struct) */
+#define PG_JOIN_INNER 0        /* INNER: matched rows only */
+#define PG_JOIN_PROBE_OUTER 4  /* LEFT:  + null-padded unmatched probe rows */
+#define PG_JOIN_LOOKUP_OUTER 5 /* RIGHT: + drain page of unmatched build rows */
+#define PG_JOIN_FULL_OUTER 6   /* FULL:  both */
+
 typedef struct {
     int64_t table;    /* handle from a finished PG_OP_HASH_BUILD */
     int32_t n_preds;
@@ -392,7 +421,51 @@ typedef struct {
      *   for each match, table.acc += proj(probe row) in exact decimal ticks
      *   AND exact-f64 fixed-point (fixed128.h); get_output after finish
      *   emits the groups page: key i64, payloads..., sum_dec i64,
-     *   sum_f64 f64 (rows = groups with >=1 match) */
+     *   sum_f64 f64 (rows = groups with >=1 match)
+     * modes 4/5/6 (PG_JOIN_PROBE_OUTER / LOOKUP_OUTER / FULL_OUTER): the
+     *   outer emit joins — LookupJoinOperator with probeOnOuterSide and
+     *   LookupOuterOperator.  Each is mode 0 plus:
+     *   4 (LEFT): a probe row that passes preds and has no match emits
+     *     one row whose payload columns are null;
+     *   5 (RIGHT): finish() queues one drain page of the build rows no
+     *     probe row of this operator matched;
+     *   6 (FULL): both.
+     *   - Predicates: probe rows failing preds emit nothing in every
+     *     mode (preds are the filter below the join), and only a probe
+     *     row that passed preds marks a build row as matched.
+     *   - Null probe keys: in modes 4 and 6 a key that is null in its
+     *     null_mask never matches; the row is emitted null-padded.  In
+     *     mode 5 it emits nothing.  Modes 0-3 do not read the key mask.
+     *     Build-key masks are out of scope in every mode (build keys
+     *     are taken as non-null).
+     *   - Row order of probe pages is mode 0's; an unmatched row sits
+     *     at its probe-row position.  Columns are the emit_probe_cols
+     *     (fixed width only) then the build payloads.
+     *   - Payload mask: in modes 4 and 6 every payload column of a probe
+     *     output page carries a device null_mask of n_rows bytes (the
+     *     payload columns share one buffer); a payload value under a
+     *     null is 0.  In mode 5 payload masks are NULL.
+     *   - Probe-column masks: in modes 4-6 an emitted probe column whose
+     *     input column has a null_mask carries it through, gathered
+     *     with the values; otherwise its null_mask is NULL.  Mode 0
+     *     drops masks.
+     *   - Drain page (modes 5, 6): exactly one, possibly of 0 rows,
+     *     queued by finish().  Rows: the unmatched build rows in
+     *     ascending build-row order (insertion order across build
+     *     pages).  Probe columns are typed as in the first page fed
+     *     (I64 when none was), hold 0 and share one all-ones mask;
+     *     payload columns hold the values, null_mask NULL.
+     *   - Match marks belong to the operator: one byte per build row,
+     *     zeroed at creation.  Several probe operators sharing one set
+     *     of marks (a partitioned probe with a single drain) is out of
+     *     scope — each operator drains what IT did not match.
+     *   - Tables: mode 4 takes every shape mode 0 takes (chained,
+     *     agg_table slot-payload incl. packed, dense_array); modes 5
+     *     and 6 take chained tables only and fail pg_op_create
+     *     otherwise.
+     *   - An empty probe page gives a 0-row page with the same columns.
+     *   - All masks are owned by the output page: valid until the next
+     *     pg_op_get_output / pg_op_destroy. */
     int32_t mode;
     int32_t n_emit;
     int32_t emit_probe_cols[8];

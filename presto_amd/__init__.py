@@ -20,7 +20,9 @@ from .engine import (  # noqa: F401
     PlanHashBuild, PlanLookupJoin, PlanTopN, PlanPartition, PlanGroupBy,
     Pred, Proj, Agg,
     CMP_LT, CMP_LE, CMP_GT, CMP_GE, CMP_EQ, CMP_NE, CMP_CONTAINS,
-    CMP_PREFIX, CMP_CONTAINS2, CMP_NOT_CONTAINS2,
+    CMP_PREFIX, CMP_CONTAINS2, CMP_NOT_CONTAINS2, CMP_IS_NULL,
+    CMP_IS_NOT_NULL,
+    JOIN_INNER, JOIN_PROBE_OUTER, JOIN_LOOKUP_OUTER, JOIN_FULL_OUTER,
     PROJ_IDENT, PROJ_DISC_PRICE, PROJ_CHARGE, PROJ_MUL, PROJ_DIV,
     PROJ_KEYSHL, PROJ_SHR, PROJ_SUBDIV, PROJ_KEYSHL_DIV,
     AGG_COUNT, AGG_SUM_F64, AGG_SUM_DEC, AGG_SUM_I64, AGG_MIN, AGG_MAX,

@@ -240,13 +240,30 @@ __device__ inline int32_t d_find(const uint8_t* d, int32_t n,
 
 /* predicate conjunction — PageFilter semantics (PageProcessor.java:299-343:
  * null comparison result excludes the row; our round-1 columns are
- * non-null, null_mask honored as exclusion) */
+ * non-null, null_mask honored as exclusion).  Every specialised kernel
+ * that bypasses this function is gated on one exact comparison op
+ * (Q1: LE, Q3 probe: GT/LT) or on n_preds == 0 (mode-2 Q5 probe), so the
+ * null tests always land here.
+ * NULL_TESTS = false compiles the null tests out: the single-scan build
+ * kernels (dense_array fills, agg_table direct insert and partition
+ * scatter — the build scan of the Q3 headline) keep exactly the code they
+ * had, and HASH_BUILD rejects a null test on those builds at create. */
+template <bool NULL_TESTS = true>
 __device__ inline bool d_eval_preds(const pg_page& pg, const pg_pred* preds,
                                     int n_preds, int64_t i)
 {
     for (int p = 0; p < n_preds; p++) {
         const pg_pred& pr = preds[p];
         const pg_col& c = pg.cols[pr.col];
+        if constexpr (NULL_TESTS) {
+            /* IS [NOT] NULL reads the mask alone (any column type, no mask
+             * = never null) and is decided before the exclusion rule */
+            if (pr.op >= PG_CMP_IS_NULL) {
+                const bool is_null = c.null_mask && c.null_mask[i];
+                if (is_null != (pr.op == PG_CMP_IS_NULL)) return false;
+                continue;
+            }
+        }
         if (c.null_mask && c.null_mask[i]) return false;
         bool ok;
         if (c.tag == PG_T_VARBIN) {
@@ -1156,7 +1173,7 @@ __global__ __launch_bounds__(256) void k_dense_fill(
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; i < pg.n_rows; i += stride) {
-        if (!d_eval_preds(pg, plan.preds, plan.n_preds, i)) continue;
+        if (!d_eval_preds<false>(pg, plan.preds, plan.n_preds, i)) continue;
         int64_t k = d_load_i64(pg.cols[plan.key_col], i);
         if (k >= 1 && k <= cap)
             out[k - 1] =
@@ -1173,7 +1190,7 @@ __global__ __launch_bounds__(256) void k_dense_fill_lu(
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; i < pg.n_rows; i += stride) {
-        if (!d_eval_preds(pg, plan.preds, plan.n_preds, i)) continue;
+        if (!d_eval_preds<false>(pg, plan.preds, plan.n_preds, i)) continue;
         int64_t k = d_load_i64(pg.cols[plan.key_col], i);
         int64_t k2 = d_load_i64(pg.cols[plan.payload_lookup_key_col], i);
         if (k >= 1 && k <= cap && k2 >= 1 && k2 <= lu_cap)
@@ -1189,7 +1206,7 @@ __global__ __launch_bounds__(256) void k_dense_fill32(
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; i < pg.n_rows; i += stride) {
-        if (!d_eval_preds(pg, plan.preds, plan.n_preds, i)) continue;
+        if (!d_eval_preds<false>(pg, plan.preds, plan.n_preds, i)) continue;
         int64_t k = d_load_i64(pg.cols[plan.key_col], i);
         if (k >= 1 && k <= cap)
             out[k - 1] = vals[i] + plan.dense_payload_bias;
@@ -1316,7 +1333,7 @@ __global__ __launch_bounds__(256) void k_tbl_insert_direct(
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     int64_t my_inserted = 0, my_overflow = 0, my_packerr = 0;
     for (; i < pg.n_rows; i += stride) {
-        if (!d_eval_preds(pg, plan.preds, plan.n_preds, i)) continue;
+        if (!d_eval_preds<false>(pg, plan.preds, plan.n_preds, i)) continue;
         uint8_t plv = 0;
         if (lu_payload) {
             /* fused dimension join: fetch u8 payload through the lookup
@@ -1461,7 +1478,7 @@ __device__ inline int d_build_eval(
     const uint8_t* lu_payload, const direct_payloads& dp, int64_t i,
     bool want_pay, build_row* out)
 {
-    if (!d_eval_preds(pg, plan.preds, plan.n_preds, i)) return 0;
+    if (!d_eval_preds<false>(pg, plan.preds, plan.n_preds, i)) return 0;
     uint8_t plv = 0;
     if (lu_payload) {
         int64_t k2 = d_load_i64(pg.cols[plan.payload_lookup_key_col], i);
@@ -2064,6 +2081,23 @@ __device__ inline int64_t d_dense_find(const uint8_t* dv8,
     return dv8[key - 1] ? key - 1 : -1;
 }
 
+/* outer-join outputs of the emit pass (modes 4-6; unused and all NULL in
+ * mode 0).  pay_null: the one mask the payload columns share (PROBE_OUTER).
+ * marks: one byte per build row, set when a probe row matched it (MARK).
+ * pmask_src/pmask_out: per emitted probe column, the input null mask and
+ * where it is gathered to (both NULL for a column without a mask). */
+struct outer_outs {
+    uint8_t* pay_null;
+    uint8_t* marks;
+    const uint8_t* pmask_src[8];
+    uint8_t* pmask_out[8];
+};
+
+/* PROBE_OUTER (modes 4, 6): a probe row that passes the predicates and
+ * has no match — a null key never matches — counts and emits one
+ * null-padded row.  MARK (modes 5, 6): matched build rows are marked for
+ * the drain; null keys are skipped.  Mode 0 is <false, false>. */
+template <bool PROBE_OUTER, bool MARK>
 __global__ __launch_bounds__(256) void k_probe_count(
     pg_page pg, pg_plan_lookup_join plan, const int64_t* keys,
     const uint8_t* tags, const int32_t* head, const int32_t* next,
@@ -2078,12 +2112,22 @@ __global__ __launch_bounds__(256) void k_probe_count(
     int64_t total = 0;
     for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
         if (!d_eval_preds(pg, plan.preds, plan.n_preds, i)) continue;
+        if constexpr (PROBE_OUTER || MARK) {
+            const uint8_t* knull = pg.cols[plan.key_col].null_mask;
+            if (knull && knull[i]) {
+                if constexpr (PROBE_OUTER) total++;
+                continue;
+            }
+        }
         int64_t key = d_load_i64(pg.cols[plan.key_col], i);
         int64_t sl;
         if (dv8 || dv32) {
             sl = d_dense_find(dv8, dv32, dcap, key);
         } else {
-            if (kbits && !d_kbit_test(kbits, bmax, key)) continue;
+            if (kbits && !d_kbit_test(kbits, bmax, key)) {
+                if constexpr (PROBE_OUTER) total++;
+                continue;
+            }
             sl = d_tbl_find_tagged(keys, tags, mask, lmask, pbits, key);
         }
         if (sl >= 0) {
@@ -2091,6 +2135,8 @@ __global__ __launch_bounds__(256) void k_probe_count(
                 for (int32_t r = head[sl]; r >= 0; r = next[r]) total++;
             else
                 total++; /* slot-payload table: unique keys */
+        } else if constexpr (PROBE_OUTER) {
+            total++;
         }
     }
     total = d_bfly_i64(total);
@@ -2110,6 +2156,27 @@ struct build_payloads {
     int32_t pack_bits; /* >0: payload[0] = keys[slot] & (2^bits-1) and the
                           emitted key = keys[slot] >> bits */
 };
+
+/* the probe columns of output row pos, from probe row i; the outer modes
+ * also gather the column's null mask */
+template <bool OUTER>
+__device__ inline void d_emit_probe_cols(const pg_page& pg,
+                                         const pg_plan_lookup_join& plan,
+                                         const emit_outs& probe_outs,
+                                         const outer_outs& oo, int64_t i,
+                                         int64_t pos)
+{
+    for (int o = 0; o < probe_outs.n; o++) {
+        pg_proj pr;
+        pr.kind = PG_PROJ_IDENT;
+        pr.a = plan.emit_probe_cols[o];
+        d_emit_val(pg, pr, i, probe_outs.ptr[o], probe_outs.tag[o], pos);
+        if constexpr (OUTER)
+            if (oo.pmask_out[o]) oo.pmask_out[o][pos] = oo.pmask_src[o][i];
+    }
+}
+
+template <bool PROBE_OUTER, bool MARK>
 __global__ __launch_bounds__(256) void k_probe_emit(
     pg_page pg, pg_plan_lookup_join plan, const int64_t* keys,
     const uint8_t* tags, const int32_t* head, const int32_t* next,
@@ -2118,8 +2185,9 @@ __global__ __launch_bounds__(256) void k_probe_emit(
     const uint8_t* dv8, const int32_t* dv32, int64_t dcap,
     int64_t chunk,
     const int64_t* block_offs, emit_outs probe_outs, build_payloads bp,
-    emit_outs build_outs)
+    emit_outs build_outs, outer_outs oo)
 {
+    constexpr bool OUTER = PROBE_OUTER || MARK;
     const int64_t n = pg.n_rows;
     const int64_t lo = (int64_t)blockIdx.x * chunk;
     const int64_t hi = min(lo + chunk, n);
@@ -2133,19 +2201,28 @@ __global__ __launch_bounds__(256) void k_probe_emit(
         int64_t sl = -1;
         int32_t c = 0;
         if (i < hi && d_eval_preds(pg, plan.preds, plan.n_preds, i)) {
-            int64_t key = d_load_i64(pg.cols[plan.key_col], i);
-            if (dv8 || dv32)
-                sl = d_dense_find(dv8, dv32, dcap, key);
-            else
-                sl = kbits && !d_kbit_test(kbits, bmax, key)
-                         ? -1
-                         : d_tbl_find_tagged(keys, tags, mask, lmask,
-                                             pbits, key);
+            bool key_ok = true;
+            if constexpr (OUTER) {
+                const uint8_t* knull = pg.cols[plan.key_col].null_mask;
+                key_ok = !(knull && knull[i]);
+            }
+            if (key_ok) {
+                int64_t key = d_load_i64(pg.cols[plan.key_col], i);
+                if (dv8 || dv32)
+                    sl = d_dense_find(dv8, dv32, dcap, key);
+                else
+                    sl = kbits && !d_kbit_test(kbits, bmax, key)
+                             ? -1
+                             : d_tbl_find_tagged(keys, tags, mask, lmask,
+                                                 pbits, key);
+            }
             if (sl >= 0) {
                 if (head)
                     for (int32_t r = head[sl]; r >= 0; r = next[r]) c++;
                 else
                     c = 1;
+            } else if constexpr (PROBE_OUTER) {
+                c = 1; /* the null-padded row */
             }
         }
         /* wave inclusive prefix of counts (stable row order) */
@@ -2164,13 +2241,7 @@ __global__ __launch_bounds__(256) void k_probe_emit(
         if (sl >= 0)
         for (int64_t r = head ? (int64_t)head[sl] : sl; r >= 0;
              r = head ? (int64_t)next[r] : -1) {
-            for (int o = 0; o < probe_outs.n; o++) {
-                pg_proj pr;
-                pr.kind = PG_PROJ_IDENT;
-                pr.a = plan.emit_probe_cols[o];
-                d_emit_val(pg, pr, i, probe_outs.ptr[o], probe_outs.tag[o],
-                           pos);
-            }
+            d_emit_probe_cols<OUTER>(pg, plan, probe_outs, oo, i, pos);
             for (int o = 0; o < bp.n; o++) {
                 int64_t pv = bp.pack_bits && o == 0
                                  ? (keys[r] &
@@ -2200,7 +2271,29 @@ __global__ __launch_bounds__(256) void k_probe_emit(
                                 : ((const uint8_t*)bp.ptr[o])[r];
                 }
             }
+            if constexpr (PROBE_OUTER) oo.pay_null[pos] = 0;
+            /* lanes that matched the same build row all store 1: benign */
+            if constexpr (MARK) oo.marks[r] = 1;
             pos++;
+        }
+        if constexpr (PROBE_OUTER) {
+            if (sl < 0 && c) { /* no match: payloads are null, values 0 */
+                d_emit_probe_cols<OUTER>(pg, plan, probe_outs, oo, i, pos);
+                for (int o = 0; o < bp.n; o++) {
+                    switch (bp.tag[o]) {
+                        case PG_T_I32:
+                            ((int32_t*)build_outs.ptr[o])[pos] = 0;
+                            break;
+                        case PG_T_I64:
+                        case PG_T_F64:
+                            ((int64_t*)build_outs.ptr[o])[pos] = 0;
+                            break;
+                        default:
+                            ((uint8_t*)build_outs.ptr[o])[pos] = 0;
+                    }
+                }
+                oo.pay_null[pos] = 1;
+            }
         }
         __syncthreads();
         if (threadIdx.x == 0)
@@ -4024,6 +4117,17 @@ struct BuildOp : Op {
     {
         t.reset(new Table());
         t->key_set_only = plan.key_set_only != 0;
+        /* the single-scan builds evaluate comparisons only (see
+         * d_eval_preds); chained builds filter through the selection
+         * path, which knows the null tests */
+        if (plan.dense_array || plan.agg_table)
+            for (int p = 0; p < plan.n_preds && p < PG_MAX_PRED; p++)
+                if (plan.preds[p].op >= PG_CMP_IS_NULL)
+                    throw std::runtime_error(
+                        "IS NULL / IS NOT NULL predicates are not "
+                        "supported on dense_array and agg_table builds "
+                        "(filter ahead of the build, or use a chained "
+                        "build)");
         if (plan.range_group) {
             if (plan.capacity_hint <= 0)
                 throw std::runtime_error(
@@ -4524,6 +4628,29 @@ struct JoinOp : Op {
     DevBuf m2_acc;       /* mode 2: [dec, flo, fhi, cnt] x 8 groups */
     DevBuf ovf;          /* modes 1/3: [tick-sum overflow, SUM_F64 addends
                             outside the 64.64 domain] */
+    /* outer joins (modes 4-6).  The match marks are this operator's own:
+     * one byte per build row, written by its probes and read once by the
+     * drain in finish(). */
+    DevBuf marks;
+    std::vector<int32_t> probe_tags; /* emitted probe columns as typed in
+                                        the first page fed (drain page) */
+    bool probe_outer() const
+    {
+        return plan.mode == PG_JOIN_PROBE_OUTER ||
+               plan.mode == PG_JOIN_FULL_OUTER;
+    }
+    bool marking() const
+    {
+        return plan.mode == PG_JOIN_LOOKUP_OUTER ||
+               plan.mode == PG_JOIN_FULL_OUTER;
+    }
+    bool outer() const { return probe_outer() || marking(); }
+    bool emit_mode() const { return plan.mode == PG_JOIN_INNER || outer(); }
+    /* a build that saw no input page never resolved its payload tags */
+    static int32_t payload_tag(const Table* tb, int o)
+    {
+        return tb->ptag[o] >= 0 ? tb->ptag[o] : PG_T_I64;
+    }
     void init()
     {
         std::lock_guard<std::mutex> lk(g_mu);
@@ -4535,12 +4662,35 @@ struct JoinOp : Op {
         if (t->key_set_only)
             throw std::runtime_error(
                 "cannot probe a key-set-only table");
-        if (t->dense && plan.mode != 0)
+        if (plan.mode < 0 || plan.mode > PG_JOIN_FULL_OUTER)
+            throw std::runtime_error("unknown LOOKUP_JOIN mode");
+        if (outer() && (plan.n_emit < 0 || plan.n_emit > 8))
+            throw std::runtime_error("n_emit must be 0..8");
+        if (outer() && t->range_group)
+            throw std::runtime_error(
+                "outer LOOKUP_JOIN modes cannot probe a range_group table");
+        if (marking()) {
+            /* the drain walks build-row arrays, which only chained tables
+             * keep (slot-payload and dense tables have no row order) */
+            if (t->slot_payloads || t->dense || !t->head.p)
+                throw std::runtime_error(
+                    plan.mode == PG_JOIN_LOOKUP_OUTER
+                        ? "LOOKUP_JOIN mode 5 (PG_JOIN_LOOKUP_OUTER) needs "
+                          "a chained build table, not an agg_table or "
+                          "dense_array"
+                        : "LOOKUP_JOIN mode 6 (PG_JOIN_FULL_OUTER) needs a "
+                          "chained build table, not an agg_table or "
+                          "dense_array");
+            marks.alloc((size_t)t->n_rows);
+            marks.zero();
+            CHKV(hipStreamSynchronize(g_stream));
+        }
+        if (t->dense && !emit_mode())
             throw std::runtime_error(
                 "dense-array tables support emit-mode joins only");
         if (t->pack_bits &&
             !(plan.mode == 1 || plan.mode == 2 ||
-              (plan.mode == 0 && t->slot_payloads)))
+              (emit_mode() && t->slot_payloads)))
             throw std::runtime_error(
                 "packed tables support fused-agg probes and slot-payload "
                 "emit joins only");
@@ -4804,38 +4954,59 @@ struct JoinOp : Op {
         }
         /* emit mode: per-block count -> host scan -> prefix emit */
         int64_t n = sp.pg.n_rows;
+        if (outer()) {
+            for (int o = 0; o < plan.n_emit; o++)
+                if (sp.pg.cols[plan.emit_probe_cols[o]].tag == PG_T_VARBIN)
+                    throw std::runtime_error(
+                        "outer LOOKUP_JOIN emits fixed-width probe "
+                        "columns only");
+            if (probe_tags.empty())
+                for (int o = 0; o < plan.n_emit; o++)
+                    probe_tags.push_back(
+                        sp.pg.cols[plan.emit_probe_cols[o]].tag);
+        }
         if (n == 0) { /* empty probe page -> empty output page */
             OutPage op;
             op.pg.n_rows = 0;
             op.pg.n_cols = plan.n_emit + (int32_t)t->payload.size();
             for (int c = 0; c < op.pg.n_cols; c++) {
                 op.pg.cols[c].tag = PG_T_I64;
+                if (outer()) /* the columns a non-empty page would have */
+                    op.pg.cols[c].tag =
+                        c < plan.n_emit ? probe_tags[c]
+                                        : payload_tag(t, c - plan.n_emit);
                 op.pg.cols[c].on_device = 1;
                 op.pg.cols[c].data = nullptr;
             }
             outq.push_back(std::move(op));
             return;
         }
+        const uint8_t* dv8 = (const uint8_t*)(
+            t->dense && t->ptag[0] == PG_T_U8 ? t->payload[0].p : nullptr);
+        const int32_t* dv32 = (const int32_t*)(
+            t->dense && t->ptag[0] == PG_T_I32 ? t->payload[0].p : nullptr);
+        const int64_t dcap = t->dense ? t->cap : 0;
         hot_begin();
         int64_t chunk = sel_chunk(n);
         DevBuf d_counts;
         d_counts.alloc(FLT_NB * 8);
-        hipLaunchKernelGGL(k_probe_count, dim3(FLT_NB), dim3(256), 0,
-                           g_stream, sp.pg, plan, (const int64_t*)t->keys.p,
-                           (const uint8_t*)t->tags.p,
-                           (const int32_t*)t->head.p,
-                           (const int32_t*)t->next.p, t->mask,
-                           t->local_mask, t->pack_bits,
-                           (const unsigned long long*)t->kbits.p, t->bmax,
-                           (const uint8_t*)(t->dense && t->ptag[0] == PG_T_U8
-                                              ? t->payload[0].p
-                                              : nullptr),
-                           (const int32_t*)(t->dense &&
-                                                    t->ptag[0] == PG_T_I32
-                                                ? t->payload[0].p
-                                                : nullptr),
-                           t->dense ? t->cap : 0, chunk,
-                           (int64_t*)d_counts.p);
+#define LAUNCH_PROBE_COUNT(PO, MK)                                       \
+    hipLaunchKernelGGL((k_probe_count<PO, MK>), dim3(FLT_NB), dim3(256), \
+                       0, g_stream, sp.pg, plan,                         \
+                       (const int64_t*)t->keys.p,                        \
+                       (const uint8_t*)t->tags.p,                        \
+                       (const int32_t*)t->head.p,                        \
+                       (const int32_t*)t->next.p, t->mask,               \
+                       t->local_mask, t->pack_bits,                      \
+                       (const unsigned long long*)t->kbits.p, t->bmax,   \
+                       dv8, dv32, dcap, chunk, (int64_t*)d_counts.p)
+        switch (plan.mode) {
+            case PG_JOIN_PROBE_OUTER: LAUNCH_PROBE_COUNT(true, false); break;
+            case PG_JOIN_LOOKUP_OUTER: LAUNCH_PROBE_COUNT(false, true); break;
+            case PG_JOIN_FULL_OUTER: LAUNCH_PROBE_COUNT(true, true); break;
+            default: LAUNCH_PROBE_COUNT(false, false);
+        }
+#undef LAUNCH_PROBE_COUNT
         std::vector<int64_t> h(FLT_NB);
         CHKV(hipMemcpyAsync(h.data(), d_counts.p, FLT_NB * 8,
                             hipMemcpyDeviceToHost, g_stream));
@@ -4855,9 +5026,11 @@ struct JoinOp : Op {
         op.pg.n_rows = total;
         emit_outs pouts{};
         pouts.n = plan.n_emit;
+        outer_outs oo{};
         int nc = 0;
         for (int o = 0; o < plan.n_emit; o++) {
-            int tag = sp.pg.cols[plan.emit_probe_cols[o]].tag;
+            const pg_col& src = sp.pg.cols[plan.emit_probe_cols[o]];
+            int tag = src.tag;
             op.dev.emplace_back();
             op.dev.back().alloc((size_t)total * type_size(tag));
             op.pg.cols[nc].tag = tag;
@@ -4865,8 +5038,21 @@ struct JoinOp : Op {
             op.pg.cols[nc].data = op.dev.back().p;
             pouts.ptr[o] = op.dev.back().p;
             pouts.tag[o] = tag;
+            if (outer() && src.null_mask) { /* mask travels with values */
+                op.dev.emplace_back();
+                op.dev.back().alloc((size_t)total);
+                oo.pmask_src[o] = src.null_mask;
+                oo.pmask_out[o] = (uint8_t*)op.dev.back().p;
+                op.pg.cols[nc].null_mask = oo.pmask_out[o];
+            }
             nc++;
         }
+        if (probe_outer()) { /* one mask shared by the payload columns */
+            op.dev.emplace_back();
+            op.dev.back().alloc((size_t)total);
+            oo.pay_null = (uint8_t*)op.dev.back().p;
+        }
+        oo.marks = (uint8_t*)marks.p;
         build_payloads bp{};
         bp.n = (int32_t)t->payload.size();
         bp.by_slot = (t->slot_payloads || t->dense) ? 1 : 0;
@@ -4874,40 +5060,109 @@ struct JoinOp : Op {
         emit_outs bouts{};
         bouts.n = bp.n;
         for (int o = 0; o < bp.n; o++) {
+            const int32_t ptag = outer() ? payload_tag(t, o) : t->ptag[o];
             bp.ptr[o] = t->payload[o].p;
-            bp.tag[o] = t->ptag[o];
+            bp.tag[o] = ptag;
             op.dev.emplace_back();
-            op.dev.back().alloc((size_t)total * type_size(t->ptag[o]));
-            op.pg.cols[nc].tag = t->ptag[o];
+            op.dev.back().alloc((size_t)total * type_size(ptag));
+            op.pg.cols[nc].tag = ptag;
             op.pg.cols[nc].on_device = 1;
             op.pg.cols[nc].data = op.dev.back().p;
+            op.pg.cols[nc].null_mask = oo.pay_null;
             bouts.ptr[o] = op.dev.back().p;
-            bouts.tag[o] = t->ptag[o];
+            bouts.tag[o] = ptag;
             nc++;
         }
         op.pg.n_cols = nc;
-        hipLaunchKernelGGL(k_probe_emit, dim3(FLT_NB), dim3(256), 0,
-                           g_stream, sp.pg, plan, (const int64_t*)t->keys.p,
-                           (const uint8_t*)t->tags.p,
-                           (const int32_t*)t->head.p,
-                           (const int32_t*)t->next.p, t->mask,
-                           t->local_mask, t->pack_bits,
-                           (const unsigned long long*)t->kbits.p, t->bmax,
-                           (const uint8_t*)(t->dense && t->ptag[0] == PG_T_U8
-                                              ? t->payload[0].p
-                                              : nullptr),
-                           (const int32_t*)(t->dense &&
-                                                    t->ptag[0] == PG_T_I32
-                                                ? t->payload[0].p
-                                                : nullptr),
-                           t->dense ? t->cap : 0, chunk,
-                           (const int64_t*)d_offs.p, pouts, bp, bouts);
+#define LAUNCH_PROBE_EMIT(PO, MK)                                        \
+    hipLaunchKernelGGL((k_probe_emit<PO, MK>), dim3(FLT_NB), dim3(256),  \
+                       0, g_stream, sp.pg, plan,                         \
+                       (const int64_t*)t->keys.p,                        \
+                       (const uint8_t*)t->tags.p,                        \
+                       (const int32_t*)t->head.p,                        \
+                       (const int32_t*)t->next.p, t->mask,               \
+                       t->local_mask, t->pack_bits,                      \
+                       (const unsigned long long*)t->kbits.p, t->bmax,   \
+                       dv8, dv32, dcap, chunk, (const int64_t*)d_offs.p, \
+                       pouts, bp, bouts, oo)
+        switch (plan.mode) {
+            case PG_JOIN_PROBE_OUTER: LAUNCH_PROBE_EMIT(true, false); break;
+            case PG_JOIN_LOOKUP_OUTER: LAUNCH_PROBE_EMIT(false, true); break;
+            case PG_JOIN_FULL_OUTER: LAUNCH_PROBE_EMIT(true, true); break;
+            default: LAUNCH_PROBE_EMIT(false, false);
+        }
+#undef LAUNCH_PROBE_EMIT
         hot_end();
         CHKV(hipStreamSynchronize(g_stream));
         outq.push_back(std::move(op));
     }
+    /* modes 5/6: the unmatched build rows, in build-row order, through the
+     * stable selection path — the build-row arrays presented as a page
+     * {marks u8, payloads...} filtered by marks == 0 */
+    void drain()
+    {
+        const int np = (int)t->payload.size();
+        pg_page bpg{};
+        bpg.n_rows = t->n_rows;
+        bpg.n_cols = 1 + np;
+        bpg.cols[0].tag = PG_T_U8;
+        bpg.cols[0].on_device = 1;
+        bpg.cols[0].data = marks.p;
+        pg_plan_filter_project fp{};
+        fp.n_preds = 1;
+        fp.preds[0].col = 0;
+        fp.preds[0].op = PG_CMP_EQ;
+        fp.preds[0].ival = 0;
+        fp.n_proj = np;
+        for (int o = 0; o < np; o++) {
+            bpg.cols[1 + o].tag = payload_tag(t, o);
+            bpg.cols[1 + o].on_device = 1;
+            bpg.cols[1 + o].data = t->payload[o].p;
+            fp.proj[o].kind = PG_PROJ_IDENT;
+            fp.proj[o].a = 1 + o;
+        }
+        int64_t chunk = sel_chunk(bpg.n_rows);
+        SelResult r = sel_count(bpg, fp, nullptr, 0, chunk);
+        OutPage op;
+        op.pg.n_rows = r.n;
+        op.pg.n_cols = plan.n_emit + np;
+        /* probe side: zeros under one shared all-ones mask */
+        op.dev.emplace_back();
+        op.dev.back().alloc((size_t)r.n);
+        uint8_t* ones = (uint8_t*)op.dev.back().p;
+        CHKV(hipMemsetAsync(ones, 1, op.dev.back().sz, g_stream));
+        for (int o = 0; o < plan.n_emit; o++) {
+            int tag = probe_tags.empty() ? PG_T_I64 : probe_tags[o];
+            op.dev.emplace_back();
+            op.dev.back().alloc((size_t)r.n * type_size(tag));
+            op.dev.back().zero();
+            op.pg.cols[o].tag = tag;
+            op.pg.cols[o].on_device = 1;
+            op.pg.cols[o].data = op.dev.back().p;
+            op.pg.cols[o].null_mask = ones;
+        }
+        emit_outs outs{};
+        outs.n = np;
+        for (int o = 0; o < np; o++) {
+            int tag = payload_tag(t, o);
+            op.dev.emplace_back();
+            op.dev.back().alloc((size_t)r.n * type_size(tag));
+            pg_col& c = op.pg.cols[plan.n_emit + o];
+            c.tag = tag;
+            c.on_device = 1;
+            c.data = op.dev.back().p;
+            outs.ptr[o] = c.data;
+            outs.tag[o] = tag;
+        }
+        sel_emit(bpg, fp, nullptr, 0, chunk, r, outs);
+        outq.push_back(std::move(op));
+    }
     void finish() override
     {
+        if (marking()) {
+            drain();
+            return;
+        }
         if (plan.mode == 2) {
             unsigned long long h[33];
             CHKV(hipMemcpy(h, m2_acc.p, sizeof(h), hipMemcpyDeviceToHost));

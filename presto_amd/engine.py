@@ -15,7 +15,11 @@ _SO = _HERE / "libpresto_gpu.so"
 # ---- enums (presto_gpu.h) ----
 T_U8, T_I32, T_I64, T_F64, T_VARBIN, T_I128 = 0, 1, 2, 3, 4, 5
 (CMP_LT, CMP_LE, CMP_GT, CMP_GE, CMP_EQ, CMP_NE, CMP_CONTAINS,
- CMP_PREFIX, CMP_CONTAINS2, CMP_NOT_CONTAINS2) = range(10)
+ CMP_PREFIX, CMP_CONTAINS2, CMP_NOT_CONTAINS2, CMP_IS_NULL,
+ CMP_IS_NOT_NULL) = range(12)
+# pg_plan_lookup_join.mode of the emit joins (PG_JOIN_*; 1-3 are the fused
+# aggregating probes)
+JOIN_INNER, JOIN_PROBE_OUTER, JOIN_LOOKUP_OUTER, JOIN_FULL_OUTER = 0, 4, 5, 6
 (PROJ_IDENT, PROJ_DISC_PRICE, PROJ_CHARGE, PROJ_MUL, PROJ_DIV,
  PROJ_KEYSHL, PROJ_SHR, PROJ_SUBDIV, PROJ_KEYSHL_DIV) = range(9)
 (AGG_COUNT, AGG_SUM_F64, AGG_SUM_DEC, AGG_SUM_I64,
@@ -236,13 +240,41 @@ class DeviceVarbin:
 class Page:
     """A Presto Page: named columns backed by numpy (host) or torch-cuda
     (device) arrays (Varbin / DeviceVarbin for variable-width columns).
-    Column order is the channel order."""
+    Column order is the channel order.  nulls maps a column name to its
+    null mask, one uint8 per row with 1 = null: a numpy array for a host
+    column, a CUDA tensor for a device column.  The page keeps the masks
+    alive, like the columns."""
 
-    def __init__(self, cols, n_rows=None):
+    def __init__(self, cols, n_rows=None, nulls=None):
         self.names = list(cols.keys())
         self.cols = cols
         first = next(iter(cols.values()))
         self.n_rows = n_rows if n_rows is not None else len(first)
+        self.nulls = {}
+        for name, m in (nulls or {}).items():
+            if name not in cols:
+                raise ValueError(f"nulls: no column {name!r}")
+            on_device = not isinstance(
+                cols[name], (np.ndarray, Varbin, DictVarbin))
+            if isinstance(m, np.ndarray) == on_device:
+                raise ValueError(
+                    f"nulls[{name!r}]: a host column takes a numpy mask, "
+                    "a device column a CUDA tensor")
+            if on_device:
+                import torch
+                ok = (isinstance(m, torch.Tensor) and m.is_cuda
+                      and m.dtype == torch.uint8 and m.dim() == 1
+                      and m.is_contiguous())
+            else:
+                ok = m.dtype == np.uint8 and m.ndim == 1 \
+                    and m.flags.c_contiguous
+            if not ok:
+                raise ValueError(f"nulls[{name!r}]: mask must be a "
+                                 "contiguous 1-d uint8 array")
+            if len(m) != self.n_rows:
+                raise ValueError(f"nulls[{name!r}]: {len(m)} entries for "
+                                 f"{self.n_rows} rows")
+            self.nulls[name] = m
 
     def channel(self, name):
         return self.names.index(name)
@@ -286,18 +318,35 @@ class Page:
                 col.tag = tagmap[a.dtype]
                 col.on_device = 1
                 col.data = a.data_ptr()
-            col.null_mask = None
+            m = self.nulls.get(name)
+            if m is None:
+                col.null_mask = None
+            elif isinstance(m, np.ndarray):
+                col.null_mask = m.ctypes.data
+            else:
+                col.null_mask = m.data_ptr()
             pg.cols[i] = col
         return pg
 
 
-def _read_output_page(cpage, names=None):
-    """Copy an output pg_page (host or device cols) into numpy arrays."""
+def _read_output_page(cpage, names=None, nulls=None):
+    """Copy an output pg_page (host or device cols) into numpy arrays.
+    With a dict passed as nulls, the null masks the page carries are
+    copied into it under the column names."""
     L = lib()
     n = cpage.n_rows
     out = {}
     for i in range(cpage.n_cols):
         col = cpage.cols[i]
+        if nulls is not None and col.null_mask:
+            m = np.empty(n, np.uint8)
+            if n:
+                if col.on_device:
+                    L.check(L.c.pg_memcpy_d2h(m.ctypes.data, col.null_mask,
+                                              n), "d2h")
+                else:
+                    C.memmove(m.ctypes.data, col.null_mask, n)
+            nulls[names[i] if names else f"c{i}"] = m
         if col.tag == T_VARBIN:
             offs = np.empty(n + 1, np.int32)
             if col.on_device:
@@ -371,6 +420,18 @@ class Operator:
         if not pp:
             return None
         return _read_output_page(pp.contents, names)
+
+    def get_output_nulls(self, names=None):
+        """get_output plus the null masks: (cols, nulls) or None, nulls
+        holding a uint8 array (1 = null) for exactly the columns whose
+        output carries a mask."""
+        L = lib()
+        pp = C.POINTER(PgPage)()
+        L.check(L.c.pg_op_get_output(self.h, C.byref(pp)), "get_output")
+        if not pp:
+            return None
+        nulls = {}
+        return _read_output_page(pp.contents, names, nulls), nulls
 
     def get_output_raw(self):
         """Returns a snapshot of the raw PgPage descriptor (device pointers

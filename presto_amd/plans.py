@@ -13,7 +13,8 @@ import ctypes as C
 from .engine import (
     Pred, Proj, Agg, PlanFilterProject, PlanHashAggSmall, PlanHashBuild,
     PlanLookupJoin, PlanGroupBy, PlanTopN, PlanPartition,
-    CMP_CONTAINS2, CMP_NOT_CONTAINS2,
+    CMP_CONTAINS2, CMP_NOT_CONTAINS2, CMP_IS_NULL, CMP_IS_NOT_NULL,
+    JOIN_PROBE_OUTER, JOIN_LOOKUP_OUTER, JOIN_FULL_OUTER,
     PROJ_IDENT, PROJ_DISC_PRICE, PROJ_CHARGE, PROJ_MUL, PROJ_DIV,
     PROJ_KEYSHL, PROJ_SUBDIV, PROJ_KEYSHL_DIV,
     AGG_COUNT, AGG_SUM_F64, AGG_SUM_DEC, AGG_SUM_I64,
@@ -49,6 +50,18 @@ def pred_varbin(col, op, needle, needle2=None):
     p.sval = sval
     p.slen = len(needle)
     return p
+
+
+def pred_is_null(col):
+    """col IS NULL: reads the column's null mask only (any column type;
+    a column without a mask is never null)."""
+    return Pred(col, CMP_IS_NULL, 0, 0.0)
+
+
+def pred_not_null(col):
+    """col IS NOT NULL; as a per-aggregate filter it makes count()
+    count(col)."""
+    return Pred(col, CMP_IS_NOT_NULL, 0, 0.0)
 
 
 # ---- projections ----
@@ -174,7 +187,8 @@ def range_group(capacity_hint):
 
 def lookup_join(table, key_col, mode, *, preds=(), filters=(), emit=(),
                 aggs=(), group_vals=(), **fields):
-    """mode 0 emits `emit` probe channels + the payloads; mode 1 is the
+    """mode 0 emits `emit` probe channels + the payloads (modes 4-6 are
+    its outer variants: left_join / right_join / full_join); mode 1 is the
     fused grouped aggregate (single proj=/dec_scale=, or aggs= with
     optional filters= and acc_pack fields); modes 2/3 take table2= etc."""
     p = PlanLookupJoin()
@@ -189,6 +203,26 @@ def lookup_join(table, key_col, mode, *, preds=(), filters=(), emit=(),
 
 def emit_join(table, key_col, emit, preds=()):
     return lookup_join(table, key_col, 0, preds=preds, emit=emit)
+
+
+def left_join(table, key_col, emit, preds=()):
+    """LEFT: emit_join plus one null-padded row per unmatched probe row;
+    the payload columns of the output carry a null mask."""
+    return lookup_join(table, key_col, JOIN_PROBE_OUTER, preds=preds,
+                       emit=emit)
+
+
+def right_join(table, key_col, emit, preds=()):
+    """RIGHT: emit_join plus, after finish(), one drain page of the build
+    rows this operator never matched (chained tables only)."""
+    return lookup_join(table, key_col, JOIN_LOOKUP_OUTER, preds=preds,
+                       emit=emit)
+
+
+def full_join(table, key_col, emit, preds=()):
+    """FULL: left_join and right_join together."""
+    return lookup_join(table, key_col, JOIN_FULL_OUTER, preds=preds,
+                       emit=emit)
 
 
 def agg_join(table, key_col, proj, dec_scale=0, preds=(), **fields):
