@@ -107,8 +107,10 @@ typedef struct {
                                  out of the outer LOOKUP_JOIN modes
                                  (PG_JOIN_PROBE_OUTER and up: null-padded
                                  payloads, gathered probe-column masks,
-                                 the drain page); every other operator
-                                 emits null_mask = NULL.  A mask follows
+                                 the drain page) and out of ORDER_BY
+                                 (gathered masks of emitted columns, and
+                                 its keys honor theirs); every other
+                                 operator emits null_mask = NULL.  A mask follows
                                  its column: host for host columns,
                                  device for device columns.
                                  pg_page_serialize / pg_page_deserialize
@@ -274,6 +276,10 @@ typedef enum {
                                  grouped aggregation over 1..4 key
                                  channels of mixed type at arbitrary
                                  cardinality (see pg_plan_groupby) */
+    PG_OP_ORDER_BY = 8,       /* OrderByOperator.java + PagesIndex.sort /
+                                 PagesIndexOrdering + SortOrder.java; with
+                                 a limit, the general TopNOperator (see
+                                 pg_plan_order_by) */
 } pg_op_kind;
 
 #define PG_MAX_PRED 8
@@ -575,6 +581,68 @@ typedef struct {
     int32_t emit_cols[8];
 } pg_plan_partition;
 
+#define PG_MAX_SORT_KEYS 4
+#define PG_MAX_SORT_EMIT 16
+typedef enum { /* SortOrder.java */
+    PG_SORT_ASC_NULLS_FIRST = 0, PG_SORT_ASC_NULLS_LAST = 1,
+    PG_SORT_DESC_NULLS_FIRST = 2, PG_SORT_DESC_NULLS_LAST = 3 } pg_sort_order;
+
+typedef struct {
+    /* PG_OP_ORDER_BY: a stable multi-key sort of the accumulated pages,
+     * entirely on the GPU, with an optional LIMIT — OrderByOperator.java
+     * over PagesIndex.sort / PagesIndexOrdering, orders per SortOrder.java.
+     *   - Lifecycle: the operator accumulates; needs_input is 1 until
+     *     finish and get_output before finish gives NULL.  finish is
+     *     idempotent and queues exactly one page, possibly of 0 rows;
+     *     is_finished turns true once that page has been taken.  Input
+     *     pages are borrowed: the key and emit columns are copied into
+     *     buffers the operator owns.  Pages may be host- or
+     *     device-resident, also mixed.  The output page is
+     *     device-resident, owned by the operator until the next
+     *     pg_op_get_output / pg_op_destroy, and can be fed raw into
+     *     another operator.
+     *   - Keys: U8, I32, I64 or F64 columns, most significant first.
+     *     Integers compare signed, U8 unsigned.  F64 orders as
+     *     Double.compare: -inf < ... < -0.0 < +0.0 < ... < +inf < NaN;
+     *     every NaN, whatever its sign or payload, equals every other NaN
+     *     and is greater than +inf.
+     *   - Nulls: a key's null_mask is honored.  Null keys go first or
+     *     last as the order says, independently of ASC/DESC, and compare
+     *     equal to each other; the value stored under a null never
+     *     influences the order.  A page without a mask for the column
+     *     contributes no nulls.
+     *   - Stability: rows that compare equal on all keys keep their input
+     *     order (page order, then row order), for ASC and DESC alike.
+     *     This is STRICTER than the reference, whose PagesIndex.sort is
+     *     not stable; it makes the output deterministic.
+     *   - Output: the emit_cols columns, in that order, permuted by the
+     *     sort.  Emit columns are fixed width (U8, I32, I64, F64, I128);
+     *     a key need not be emitted and a column may be emitted twice.
+     *     Values are copied bit for bit (NaN payloads, -0.0 and values
+     *     under nulls survive).  An emitted column that had a null_mask
+     *     on any input page carries a gathered device mask (pages
+     *     without one contribute zeros); otherwise its null_mask is NULL.
+     *     With no page fed at all, the 0-row page types its columns I64;
+     *     otherwise the types are the first page's.
+     *   - Limit: limit > 0 keeps the first min(limit, n) sorted rows;
+     *     0 means no limit.
+     *   - Errors at create, naming the field: n_keys outside 1..4, n_emit
+     *     outside 1..16, an unknown order, a negative limit, a negative
+     *     column index.  Errors at add_input, naming the column: an index
+     *     >= n_cols, a VARBIN or dictionary key or emit column, an I128
+     *     key, a type that differs from the first page's.  More than
+     *     2^31-1 accumulated rows is an error (row ids are 32-bit).
+     *   - Out of scope: variable-width keys or emit columns; I128 keys;
+     *     expression keys (project them first through FILTER_PROJECT); a
+     *     preselection fast path for small limits; spilling. */
+    int32_t n_keys;                    /* 1..4, most significant first */
+    int32_t key_col[PG_MAX_SORT_KEYS];
+    int32_t order[PG_MAX_SORT_KEYS];   /* pg_sort_order */
+    int32_t n_emit;                    /* 1..16 */
+    int32_t emit_cols[PG_MAX_SORT_EMIT];
+    int64_t limit;                     /* 0 = none; >0: first `limit` rows */
+} pg_plan_order_by;
+
 /* ---- operator lifecycle (Operator.java:20-102 analog) ---- */
 typedef int64_t pg_op;
 
@@ -635,6 +703,14 @@ pg_status pg_page_serialize(const pg_page* page /* host cols */,
  * pg_plan_partition}; returns how many it would fill.  Bindings compare
  * against their own struct sizes at load time. */
 int32_t pg_abi_struct_sizes(int32_t* out, int32_t n);
+/* sizeof the plan struct of an operator kind (all eight pg_op_kind values,
+ * pg_plan_order_by included), or -1 for an unknown kind. */
+int32_t pg_abi_plan_size(int32_t kind);
+/* the order-preserving key transform of PG_OP_ORDER_BY (csrc/sortkey.h,
+ * the code k_sort_encode runs on the device): the u64 whose unsigned
+ * order is the pg_sort_order of a `tag` column value with bit pattern
+ * `bits`.  Host-only, needs no GPU — test plumbing */
+uint64_t pg_sortkey_u64(int32_t tag, int32_t order, uint64_t bits);
 
 pg_status pg_page_serialize2(const pg_page* page, int32_t compress,
                              void* out, int64_t cap, int64_t* out_len);

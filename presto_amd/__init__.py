@@ -27,6 +27,8 @@ from .engine import (  # noqa: F401
     PROJ_KEYSHL, PROJ_SHR, PROJ_SUBDIV, PROJ_KEYSHL_DIV,
     AGG_COUNT, AGG_SUM_F64, AGG_SUM_DEC, AGG_SUM_I64, AGG_MIN, AGG_MAX,
     OP_FILTER_PROJECT, OP_HASH_AGG_SMALL, OP_HASH_BUILD, OP_LOOKUP_JOIN,
-    OP_TOPN, OP_PARTITION, OP_GROUPBY_MULTI,
+    OP_TOPN, OP_PARTITION, OP_GROUPBY_MULTI, OP_ORDER_BY,
+    PlanOrderBy, SORT_ASC_NULLS_FIRST, SORT_ASC_NULLS_LAST,
+    SORT_DESC_NULLS_FIRST, SORT_DESC_NULLS_LAST,
 )
 from . import pipelines, plans  # noqa: F401

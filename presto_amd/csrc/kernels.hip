@@ -20,9 +20,11 @@
 #include <algorithm>
 #include <type_traits>
 #include <stdexcept>
+#include <string>
 
 #include "../../include/presto_gpu.h"
 #include "fixed128.h"
+#include "sortkey.h"
 
 /* ------------------------------------------------------------------ */
 /* error handling                                                     */
@@ -3346,6 +3348,244 @@ __global__ __launch_bounds__(256) void k_part_emit(pg_page pg,
     }
 }
 
+/* ------------------------------------------------------------------ */
+/* ORDER BY — OrderByOperator.java over PagesIndex.sort /             */
+/* PagesIndexOrdering, orders per SortOrder.java.  A least-significant */
+/* -digit radix sort, 8-bit digits, over (u64 sortable key, u32 row   */
+/* id) pairs in ping-pong buffers.  Keys are processed last to first; */
+/* every pass is stable, which yields the multi-key order and keeps   */
+/* ties in input order (stricter than the reference's sort).          */
+/* ------------------------------------------------------------------ */
+#define SORT_WINDOW 256      /* rows one block ranks per step */
+#define SORT_MIN_WINDOWS 4   /* a block's chunk is at least this many */
+#define SORT_NB 1024         /* most blocks a pass launches */
+
+/* keys[i] = sortable key of column[rowid[i]] (sortkey.h).  rowid NULL is
+ * the first key processed: the identity, which also seeds ids.  A row
+ * that is null in the key's mask encodes as 0, so the value under a null
+ * never reaches the sort.  mask_mode: the key is the gathered mask byte
+ * itself, turned into the two bins of the NULLS FIRST/LAST pass. */
+__global__ __launch_bounds__(256) void k_sort_encode(
+    const void* col, int tag, int order, const uint8_t* mask, int mask_mode,
+    const uint32_t* rowid, uint32_t* ids, uint64_t* keys, int64_t n)
+{
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n;
+         i += stride) {
+        uint32_t r = rowid ? rowid[i] : (uint32_t)i;
+        if (!rowid) ids[i] = r;
+        bool null = mask && mask[r];
+        uint64_t k;
+        if (mask_mode) {
+            /* order & 1: NULLS LAST */
+            k = null == (bool)(order & 1) ? 1 : 0;
+        } else if (null) {
+            k = 0;
+        } else {
+            uint64_t bits;
+            switch (tag) {
+                case PG_T_U8: bits = ((const uint8_t*)col)[r]; break;
+                case PG_T_I32: bits = ((const uint32_t*)col)[r]; break;
+                default: bits = ((const uint64_t*)col)[r]; break;
+            }
+            k = pg_sortkey(tag, order, bits);
+        }
+        keys[i] = k;
+    }
+}
+
+/* one read of the keys -> the 8 x 256 global digit histograms.  LDS
+ * atomics per block, then one global add per non-empty bin.  A byte on
+ * which a whole wave agrees (the common case for the high bytes) costs
+ * one LDS add for the wave, not 64 colliding ones. */
+__global__ __launch_bounds__(256) void k_sort_digits(const uint64_t* keys,
+                                                     int64_t n,
+                                                     uint32_t* hist)
+{
+    __shared__ uint32_t h[8 * 256];
+    for (int p = threadIdx.x; p < 8 * 256; p += 256) h[p] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    /* whole waves enter together so the ballots are uniform */
+    for (int64_t base = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63);
+         base < n; base += stride) {
+        int64_t i = base + lane;
+        bool valid = i < n;
+        uint64_t k = valid ? keys[i] : 0;
+        uint64_t act = d_ballot(valid);
+        /* base < n, so lane 0 is always a valid row: compare with it */
+        uint32_t f_lo = __shfl((uint32_t)k, 0);
+        uint32_t f_hi = __shfl((uint32_t)(k >> 32), 0);
+        uint64_t x = k ^ (((uint64_t)f_hi << 32) | f_lo);
+        for (int b = 0; b < 8; b++) {
+            int d = (int)(k >> (8 * b)) & 255;
+            bool differs = valid && ((x >> (8 * b)) & 255) != 0;
+            if (d_ballot(differs) == 0) {
+                if (lane == 0)
+                    atomicAdd(&h[b * 256 + d], (uint32_t)__popcll(act));
+            } else if (valid) {
+                atomicAdd(&h[b * 256 + d], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (int p = threadIdx.x; p < 8 * 256; p += 256)
+        if (h[p]) atomicAdd(&hist[p], h[p]);
+}
+
+/* per pass: block b owns rows [b*chunk, (b+1)*chunk) and writes its 256
+ * bin counts, digit-major (counts[d * nb + b]) — the order the scan
+ * wants */
+__global__ __launch_bounds__(256) void k_radix_count(const uint64_t* keys,
+                                                     int64_t n, int shift,
+                                                     int64_t chunk,
+                                                     uint32_t* counts)
+{
+    __shared__ uint32_t h[256];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t lo = (int64_t)blockIdx.x * chunk;
+    const int64_t hi = min(lo + chunk, n);
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256)
+        atomicAdd(&h[(keys[i] >> shift) & 255], 1u);
+    __syncthreads();
+    counts[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = h[threadIdx.x];
+}
+
+/* exclusive scan of the counters in digit-major, block-minor order, in
+ * place, one block per digit: afterwards counts[d * nb + b] is where
+ * block b's first row of digit d goes.  Block d starts at the number of
+ * rows with a smaller digit, which it reads off the pass's global
+ * histogram (totals[256], from k_sort_digits over the same keys), and
+ * scans its own row of nb <= SORT_NB block counts. */
+__global__ __launch_bounds__(256) void k_radix_scan(uint32_t* counts, int nb,
+                                                    const uint32_t* totals)
+{
+    __shared__ uint32_t part[256];
+    __shared__ uint32_t below[256];
+    const int d = blockIdx.x, t = threadIdx.x;
+    uint32_t* row = counts + (size_t)d * nb;
+    const int per = (nb + 255) / 256;
+    const int lo = min(t * per, nb);
+    const int hi = min(lo + per, nb);
+    uint32_t s = 0;
+    for (int i = lo; i < hi; i++) s += row[i];
+    part[t] = s;
+    below[t] = t < d ? totals[t] : 0;
+    __syncthreads();
+    /* Hillis-Steele inclusive scans of the per-thread sums and of the
+     * smaller digits' totals */
+    for (int off = 1; off < 256; off <<= 1) {
+        uint32_t v = t >= off ? part[t - off] : 0;
+        uint32_t b = t >= off ? below[t - off] : 0;
+        __syncthreads();
+        part[t] += v;
+        below[t] += b;
+        __syncthreads();
+    }
+    uint32_t run = below[255] + part[t] - s;
+    for (int i = lo; i < hi; i++) {
+        uint32_t c = row[i];
+        row[i] = run;
+        run += c;
+    }
+}
+
+/* the stable scatter.  Geometry of k_part_emit: a block walks its chunk
+ * in SORT_WINDOW-row windows with running[256] in LDS and per-wave bin
+ * counts wcnt[4][256]; a row lands at running[d] + the counts of the
+ * waves before its own + its rank among the same-digit lanes below it.
+ * The same-digit peer mask comes from 8 ballots, one per digit bit (each
+ * ANDed in as is or complemented, by the lane's own bit), not from one
+ * ballot per bin.  Lanes past the end of the chunk are taken out by the
+ * ballot of `valid`, so they match nobody. */
+__global__ __launch_bounds__(256) void k_radix_scatter(
+    const uint64_t* keys_in, const uint32_t* ids_in, uint64_t* keys_out,
+    uint32_t* ids_out, int64_t n, int shift, int64_t chunk,
+    const uint32_t* offs)
+{
+    __shared__ uint32_t running[256];
+    __shared__ uint32_t wcnt[4][256];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int64_t lo = (int64_t)blockIdx.x * chunk;
+    const int64_t hi = min(lo + chunk, n);
+    running[threadIdx.x] = offs[(size_t)threadIdx.x * gridDim.x + blockIdx.x];
+    for (int w = 0; w < 4; w++) wcnt[w][threadIdx.x] = 0;
+    __syncthreads();
+    for (int64_t base = lo; base < hi; base += SORT_WINDOW) {
+        int64_t i = base + threadIdx.x;
+        bool valid = i < hi;
+        uint64_t k = valid ? keys_in[i] : 0;
+        uint32_t id = valid ? ids_in[i] : 0;
+        int d = (int)(k >> shift) & 255;
+        uint64_t peers = d_ballot(valid);
+        for (int b = 0; b < 8; b++) {
+            bool bit = (d >> b) & 1;
+            uint64_t m = d_ballot(bit);
+            peers &= bit ? m : ~m;
+        }
+        int rank = __popcll(peers & ((1ull << lane) - 1));
+        if (valid && rank == 0) wcnt[wid][d] = (uint32_t)__popcll(peers);
+        __syncthreads();
+        if (valid) {
+            uint32_t pos = running[d] + rank;
+            for (int w = 0; w < wid; w++) pos += wcnt[w][d];
+            keys_out[pos] = k;
+            ids_out[pos] = id;
+        }
+        __syncthreads();
+        /* thread t owns bin t: fold the window in and clear it */
+        uint32_t add = 0;
+        for (int w = 0; w < 4; w++) {
+            add += wcnt[w][threadIdx.x];
+            wcnt[w][threadIdx.x] = 0;
+        }
+        running[threadIdx.x] += add;
+        __syncthreads();
+    }
+}
+
+/* out[c][i] = in[c][rowid[i]] for i < n_out (the limit), per emit column
+ * of width 1, 4, 8 or 16 bytes, and for the masks */
+struct sort_gather_cols {
+    int n;
+    const void* src[PG_MAX_SORT_EMIT];
+    void* dst[PG_MAX_SORT_EMIT];
+    int width[PG_MAX_SORT_EMIT];
+    const uint8_t* msrc[PG_MAX_SORT_EMIT]; /* NULL: column has no mask */
+    uint8_t* mdst[PG_MAX_SORT_EMIT];
+};
+
+__global__ __launch_bounds__(256) void k_sort_gather(const uint32_t* rowid,
+                                                     int64_t n_out,
+                                                     sort_gather_cols g)
+{
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_out;
+         i += stride) {
+        uint32_t r = rowid[i];
+        for (int c = 0; c < g.n; c++) {
+            switch (g.width[c]) {
+                case 1:
+                    ((uint8_t*)g.dst[c])[i] = ((const uint8_t*)g.src[c])[r];
+                    break;
+                case 4:
+                    ((uint32_t*)g.dst[c])[i] = ((const uint32_t*)g.src[c])[r];
+                    break;
+                case 8:
+                    ((uint64_t*)g.dst[c])[i] = ((const uint64_t*)g.src[c])[r];
+                    break;
+                default:
+                    ((ulonglong2*)g.dst[c])[i] =
+                        ((const ulonglong2*)g.src[c])[r];
+                    break;
+            }
+            if (g.msrc[c]) g.mdst[c][i] = g.msrc[c][r];
+        }
+    }
+}
+
 /* ================================================================== */
 /* host side: operator state machines + C-ABI                         */
 /* ================================================================== */
@@ -5692,6 +5932,292 @@ struct PartitionOp : Op {
     }
 };
 
+/* ---------------- ORDER_BY ---------------- */
+struct OrderByOp : Op {
+    pg_plan_order_by plan;
+    /* one slot per distinct input column the plan names, as key, as emit
+     * column or both: the per-page copies, then the concatenation */
+    struct Slot {
+        int col = 0;
+        int tag = PG_T_I64; /* the first page's; I64 until one is fed */
+        bool has_mask = false;
+        std::vector<DevBuf> data, mask; /* per page; mask unallocated
+                                           where the page had none */
+        DevBuf all, all_mask;
+    };
+    std::vector<Slot> slots;
+    int key_slot[PG_MAX_SORT_KEYS], emit_slot[PG_MAX_SORT_EMIT];
+    std::vector<int64_t> page_rows;
+    int64_t n_total = 0;
+    bool typed = false;
+
+    static std::string fname(const char* field, int i)
+    {
+        return std::string("ORDER_BY: ") + field + "[" + std::to_string(i) +
+               "]";
+    }
+    int slot_of(int col)
+    {
+        for (size_t s = 0; s < slots.size(); s++)
+            if (slots[s].col == col) return (int)s;
+        slots.emplace_back();
+        slots.back().col = col;
+        return (int)slots.size() - 1;
+    }
+    void init()
+    {
+        if (plan.n_keys < 1 || plan.n_keys > PG_MAX_SORT_KEYS)
+            throw std::runtime_error("ORDER_BY: n_keys must be 1..4");
+        if (plan.n_emit < 1 || plan.n_emit > PG_MAX_SORT_EMIT)
+            throw std::runtime_error("ORDER_BY: n_emit must be 1..16");
+        if (plan.limit < 0)
+            throw std::runtime_error("ORDER_BY: limit must be >= 0");
+        for (int i = 0; i < plan.n_keys; i++) {
+            if (plan.order[i] < PG_SORT_ASC_NULLS_FIRST ||
+                plan.order[i] > PG_SORT_DESC_NULLS_LAST)
+                throw std::runtime_error(fname("order", i) +
+                                         " is not a pg_sort_order");
+            if (plan.key_col[i] < 0)
+                throw std::runtime_error(fname("key_col", i) +
+                                         " is negative");
+        }
+        for (int i = 0; i < plan.n_emit; i++)
+            if (plan.emit_cols[i] < 0)
+                throw std::runtime_error(fname("emit_cols", i) +
+                                         " is negative");
+        for (int i = 0; i < plan.n_keys; i++)
+            key_slot[i] = slot_of(plan.key_col[i]);
+        for (int i = 0; i < plan.n_emit; i++)
+            emit_slot[i] = slot_of(plan.emit_cols[i]);
+    }
+    void check_col(const pg_page* in, const std::string& name, int c,
+                   bool is_key)
+    {
+        if (c >= in->n_cols)
+            throw std::runtime_error(name + " = " + std::to_string(c) +
+                                     " is not a column of the page (n_cols " +
+                                     std::to_string(in->n_cols) + ")");
+        const pg_col& col = in->cols[c];
+        if (col.tag == PG_T_VARBIN || col.dict_ids)
+            throw std::runtime_error(name + ": VARBIN and dictionary "
+                                     "columns are unsupported");
+        if (col.tag == PG_T_I128 && is_key)
+            throw std::runtime_error(name + ": I128 keys are unsupported");
+        if (col.tag != PG_T_U8 && col.tag != PG_T_I32 &&
+            col.tag != PG_T_I64 && col.tag != PG_T_F64 &&
+            col.tag != PG_T_I128)
+            throw std::runtime_error(name + ": unknown column type " +
+                                     std::to_string(col.tag));
+        const Slot& s = slots[slot_of(c)];
+        if (typed && s.tag != col.tag)
+            throw std::runtime_error(
+                name + ": type " + std::to_string(col.tag) +
+                " differs from the first page's " + std::to_string(s.tag));
+    }
+    void add_input(const pg_page* in) override
+    {
+        /* every check before the first copy: a rejected page leaves the
+         * operator as it was */
+        if (in->n_rows < 0) throw std::runtime_error("ORDER_BY: n_rows < 0");
+        for (int i = 0; i < plan.n_keys; i++)
+            check_col(in, fname("key_col", i), plan.key_col[i], true);
+        for (int i = 0; i < plan.n_emit; i++)
+            check_col(in, fname("emit_cols", i), plan.emit_cols[i], false);
+        const int64_t n = in->n_rows;
+        if (n_total + n > INT32_MAX)
+            throw std::runtime_error("ORDER_BY: more than 2^31-1 accumulated "
+                                     "rows (row ids are 32-bit)");
+        for (auto& s : slots) {
+            const pg_col& col = in->cols[s.col];
+            s.tag = col.tag;
+            hipMemcpyKind kind = col.on_device ? hipMemcpyDeviceToDevice
+                                               : hipMemcpyHostToDevice;
+            s.data.emplace_back();
+            s.mask.emplace_back();
+            size_t nb = (size_t)n * type_size(col.tag);
+            s.data.back().alloc(nb);
+            if (nb)
+                CHKV(hipMemcpyAsync(s.data.back().p, col.data, nb, kind,
+                                    g_stream));
+            if (col.null_mask) {
+                s.has_mask = true;
+                s.mask.back().alloc((size_t)n);
+                if (n)
+                    CHKV(hipMemcpyAsync(s.mask.back().p, col.null_mask,
+                                        (size_t)n, kind, g_stream));
+            }
+        }
+        /* the page is borrowed for the call only */
+        CHKV(hipStreamSynchronize(g_stream));
+        typed = true;
+        page_rows.push_back(n);
+        n_total += n;
+    }
+    /* per-page copies -> one column; a page without a mask contributes
+     * zeros to a column that has one */
+    void concat(Slot& s)
+    {
+        const size_t w = type_size(s.tag);
+        if (s.data.size() == 1) {
+            s.all = std::move(s.data[0]);
+        } else {
+            s.all.alloc((size_t)n_total * w);
+            size_t off = 0;
+            for (size_t p = 0; p < s.data.size(); p++) {
+                size_t nb = (size_t)page_rows[p] * w;
+                if (nb)
+                    CHKV(hipMemcpyAsync((int8_t*)s.all.p + off, s.data[p].p,
+                                        nb, hipMemcpyDeviceToDevice,
+                                        g_stream));
+                off += nb;
+            }
+        }
+        if (s.has_mask) {
+            s.all_mask.alloc((size_t)n_total);
+            s.all_mask.zero();
+            size_t off = 0;
+            for (size_t p = 0; p < s.mask.size(); p++) {
+                if (s.mask[p].p && page_rows[p])
+                    CHKV(hipMemcpyAsync((int8_t*)s.all_mask.p + off,
+                                        s.mask[p].p, (size_t)page_rows[p],
+                                        hipMemcpyDeviceToDevice, g_stream));
+                off += (size_t)page_rows[p];
+            }
+        }
+        /* stream order: the chunks go back to the pool only after the
+         * copies out of them are queued, and the pool's next user runs
+         * on the same stream */
+        s.data.clear();
+        s.mask.clear();
+    }
+    /* the sorted permutation of [0, n) for n >= 2: a fixed launch
+     * sequence on g_stream with one host read (the digit histograms) per
+     * key.  Returns which of the two id buffers holds it. */
+    uint32_t* sort_ids(int64_t n, DevBuf& idA, DevBuf& idB)
+    {
+        DevBuf kA, kB, hist, counts;
+        kA.alloc((size_t)n * 8);
+        kB.alloc((size_t)n * 8);
+        hist.alloc(8 * 256 * 4);
+        int64_t chunk = (n + SORT_NB - 1) / SORT_NB;
+        chunk = (chunk + SORT_WINDOW - 1) / SORT_WINDOW * SORT_WINDOW;
+        chunk = std::max<int64_t>(chunk, SORT_MIN_WINDOWS * SORT_WINDOW);
+        const int nb = (int)((n + chunk - 1) / chunk);
+        counts.alloc((size_t)256 * nb * 4);
+        const int sgrid = (int)std::min<int64_t>((n + 255) / 256, 2048);
+        uint64_t *kin = (uint64_t*)kA.p, *kout = (uint64_t*)kB.p;
+        uint32_t *iin = (uint32_t*)idA.p, *iout = (uint32_t*)idB.p;
+        /* one pass over digit `shift / 8`; hist holds the histograms of
+         * the keys being sorted */
+        auto pass = [&](int shift) {
+            hipLaunchKernelGGL(k_radix_count, dim3(nb), dim3(256), 0,
+                               g_stream, kin, n, shift, chunk,
+                               (uint32_t*)counts.p);
+            hipLaunchKernelGGL(k_radix_scan, dim3(256), dim3(256), 0,
+                               g_stream, (uint32_t*)counts.p, nb,
+                               (const uint32_t*)hist.p + shift / 8 * 256);
+            hipLaunchKernelGGL(k_radix_scatter, dim3(nb), dim3(256), 0,
+                               g_stream, kin, iin, kout, iout, n, shift,
+                               chunk, (const uint32_t*)counts.p);
+            std::swap(kin, kout);
+            std::swap(iin, iout);
+        };
+        std::vector<uint32_t> h(8 * 256);
+        for (int k = plan.n_keys - 1; k >= 0; k--) {
+            const Slot& s = slots[key_slot[k]];
+            const uint8_t* mask =
+                s.has_mask ? (const uint8_t*)s.all_mask.p : nullptr;
+            const bool first = k == plan.n_keys - 1;
+            hipLaunchKernelGGL(k_sort_encode, dim3(sgrid), dim3(256), 0,
+                               g_stream, (const void*)s.all.p, s.tag,
+                               plan.order[k], mask, 0,
+                               first ? (const uint32_t*)nullptr : iin, iin,
+                               kin, n);
+            hist.zero();
+            hipLaunchKernelGGL(k_sort_digits, dim3(sgrid), dim3(256), 0,
+                               g_stream, kin, n, (uint32_t*)hist.p);
+            CHKV(hipMemcpyAsync(h.data(), hist.p, 8 * 256 * 4,
+                                hipMemcpyDeviceToHost, g_stream));
+            CHKV(hipStreamSynchronize(g_stream));
+            for (int p = 0; p < 8; p++) {
+                /* a digit on which every row agrees moves nothing */
+                bool one_bin = false;
+                for (int d = 0; d < 256 && !one_bin; d++)
+                    one_bin = h[p * 256 + d] == (uint32_t)n;
+                if (!one_bin) pass(8 * p);
+            }
+            if (mask) {
+                /* NULLS FIRST/LAST: the key's most significant pass, two
+                 * bins over the gathered mask byte */
+                hipLaunchKernelGGL(k_sort_encode, dim3(sgrid), dim3(256), 0,
+                                   g_stream, (const void*)s.all.p, s.tag,
+                                   plan.order[k], mask, 1,
+                                   (const uint32_t*)iin, iin, kin, n);
+                hist.zero();
+                hipLaunchKernelGGL(k_sort_digits, dim3(sgrid), dim3(256), 0,
+                                   g_stream, kin, n, (uint32_t*)hist.p);
+                pass(0);
+            }
+        }
+        CHKV(hipStreamSynchronize(g_stream)); /* before kA/kB are pooled */
+        return iin;
+    }
+    void finish() override
+    {
+        const int64_t n = n_total;
+        for (auto& s : slots) concat(s);
+        DevBuf idA, idB;
+        const uint32_t* ids = nullptr;
+        if (n >= 2) {
+            idA.alloc((size_t)n * 4);
+            idB.alloc((size_t)n * 4);
+            ids = sort_ids(n, idA, idB);
+        } else if (n == 1) {
+            idA.alloc(4);
+            idA.zero(); /* the one row is row 0 */
+            ids = (const uint32_t*)idA.p;
+        }
+        const int64_t n_out = plan.limit > 0 ? std::min(plan.limit, n) : n;
+        OutPage op;
+        op.pg.n_rows = n_out;
+        op.pg.n_cols = plan.n_emit;
+        sort_gather_cols g{};
+        g.n = plan.n_emit;
+        for (int o = 0; o < plan.n_emit; o++) {
+            const Slot& s = slots[emit_slot[o]];
+            const size_t w = type_size(s.tag);
+            op.dev.emplace_back();
+            op.dev.back().alloc((size_t)n_out * w);
+            g.src[o] = s.all.p;
+            g.dst[o] = op.dev.back().p;
+            g.width[o] = (int)w;
+            op.pg.cols[o].tag = s.tag;
+            op.pg.cols[o].on_device = 1;
+            op.pg.cols[o].data = g.dst[o];
+            op.pg.cols[o].null_mask = nullptr;
+            if (s.has_mask) {
+                op.dev.emplace_back();
+                op.dev.back().alloc((size_t)n_out);
+                g.msrc[o] = (const uint8_t*)s.all_mask.p;
+                g.mdst[o] = (uint8_t*)op.dev.back().p;
+                op.pg.cols[o].null_mask = g.mdst[o];
+            }
+        }
+        if (n_out > 0) {
+            const int grid =
+                (int)std::min<int64_t>((n_out + 255) / 256, 2048);
+            hipLaunchKernelGGL(k_sort_gather, dim3(grid), dim3(256), 0,
+                               g_stream, ids, n_out, g);
+        }
+        CHKV(hipStreamSynchronize(g_stream));
+        for (auto& s : slots) {
+            s.all.free();
+            s.all_mask.free();
+        }
+        outq.push_back(std::move(op));
+    }
+};
+
 /* shared_ptr so a concurrent pg_op_destroy cannot free an Op another
  * thread's call still holds (each C-ABI entry copies the ref; the
  * per-handle single-threaded contract of presto_gpu.h still applies to
@@ -5767,6 +6293,15 @@ extern "C" pg_status pg_op_create(int32_t kind, const void* plan,
                 memcpy(&o->plan, plan, sizeof(o->plan));
                 o->init();
                 op.reset(o);
+                break;
+            }
+            case PG_OP_ORDER_BY: {
+                if (plan_bytes != sizeof(pg_plan_order_by))
+                    return seterr("bad plan size");
+                auto* o = new OrderByOp();
+                op.reset(o);
+                memcpy(&o->plan, plan, sizeof(o->plan));
+                o->init();
                 break;
             }
             default: return seterr("unknown operator kind");
@@ -6377,6 +6912,28 @@ extern "C" int32_t pg_abi_struct_sizes(int32_t* out, int32_t n)
     const int32_t count = (int32_t)(sizeof(sz) / sizeof(sz[0]));
     for (int32_t i = 0; i < n && i < count; i++) out[i] = sz[i];
     return count;
+}
+
+extern "C" int32_t pg_abi_plan_size(int32_t kind)
+{
+    switch (kind) {
+        case PG_OP_FILTER_PROJECT:
+            return (int32_t)sizeof(pg_plan_filter_project);
+        case PG_OP_HASH_AGG_SMALL:
+            return (int32_t)sizeof(pg_plan_hash_agg_small);
+        case PG_OP_HASH_BUILD: return (int32_t)sizeof(pg_plan_hash_build);
+        case PG_OP_LOOKUP_JOIN: return (int32_t)sizeof(pg_plan_lookup_join);
+        case PG_OP_TOPN: return (int32_t)sizeof(pg_plan_topn);
+        case PG_OP_PARTITION: return (int32_t)sizeof(pg_plan_partition);
+        case PG_OP_GROUPBY_MULTI: return (int32_t)sizeof(pg_plan_groupby);
+        case PG_OP_ORDER_BY: return (int32_t)sizeof(pg_plan_order_by);
+        default: return -1;
+    }
+}
+
+extern "C" uint64_t pg_sortkey_u64(int32_t tag, int32_t order, uint64_t bits)
+{
+    return pg_sortkey(tag, order, bits);
 }
 
 extern "C" pg_status pg_page_serialize2(const pg_page* page,

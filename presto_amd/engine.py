@@ -25,7 +25,10 @@ JOIN_INNER, JOIN_PROBE_OUTER, JOIN_LOOKUP_OUTER, JOIN_FULL_OUTER = 0, 4, 5, 6
 (AGG_COUNT, AGG_SUM_F64, AGG_SUM_DEC, AGG_SUM_I64,
  AGG_MIN, AGG_MAX) = range(6)
 (OP_FILTER_PROJECT, OP_HASH_AGG_SMALL, OP_HASH_BUILD, OP_LOOKUP_JOIN,
- OP_TOPN, OP_PARTITION, OP_GROUPBY_MULTI) = range(1, 8)
+ OP_TOPN, OP_PARTITION, OP_GROUPBY_MULTI, OP_ORDER_BY) = range(1, 9)
+# pg_sort_order (SortOrder.java)
+(SORT_ASC_NULLS_FIRST, SORT_ASC_NULLS_LAST, SORT_DESC_NULLS_FIRST,
+ SORT_DESC_NULLS_LAST) = range(4)
 
 _NP_TAG = {np.dtype(np.uint8): T_U8, np.dtype(np.int32): T_I32,
            np.dtype(np.int64): T_I64, np.dtype(np.float64): T_F64}
@@ -122,6 +125,12 @@ class PlanPartition(C.Structure):
                 ("n_emit", C.c_int32), ("emit_cols", C.c_int32 * 8)]
 
 
+class PlanOrderBy(C.Structure):
+    _fields_ = [("n_keys", C.c_int32), ("key_col", C.c_int32 * 4),
+                ("order", C.c_int32 * 4), ("n_emit", C.c_int32),
+                ("emit_cols", C.c_int32 * 16), ("limit", C.c_int64)]
+
+
 class _Lib:
     def __init__(self):
         if not _SO.exists():
@@ -148,6 +157,10 @@ class _Lib:
         self.c.pg_memcpy_d2d.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         self.c.pg_memcpy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         self.c.pg_device_sync.argtypes = []
+        self.c.pg_abi_plan_size.argtypes = [C.c_int32]
+        self.c.pg_abi_plan_size.restype = C.c_int32
+        self.c.pg_sortkey_u64.argtypes = [C.c_int32, C.c_int32, C.c_uint64]
+        self.c.pg_sortkey_u64.restype = C.c_uint64
 
     def err(self):
         return (self.c.pg_last_error() or b"").decode()

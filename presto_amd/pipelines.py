@@ -27,7 +27,7 @@ from . import plans as pl
 from .engine import (
     Page, Scope,
     OP_FILTER_PROJECT, OP_GROUPBY_MULTI, OP_HASH_AGG_SMALL, OP_LOOKUP_JOIN,
-    OP_TOPN,
+    OP_ORDER_BY, OP_TOPN,
     CMP_LE, CMP_LT, CMP_GT, CMP_GE, CMP_EQ, CMP_NE, CMP_CONTAINS,
     CMP_PREFIX, CMP_CONTAINS2, CMP_NOT_CONTAINS2,
 )
@@ -580,8 +580,8 @@ def q11(supp: Page, ps: Page, n_part: int):
     0.0001*total; ORDER BY value DESC (partkey ASC tiebreak).  The MUL
     decimal projection yields 1e-4 ticks (cents x hundredth-encoded
     qty); the strict HAVING threshold total/10000 becomes a plan
-    constant.  Returns (partkeys, value_cents) host arrays; the ~1k-row
-    final ORDER BY runs host-side (output-stage sort)."""
+    constant.  The final ORDER BY is an ORDER_BY operator over the HAVING
+    filter's device page.  Returns (partkeys, value_cents) host arrays."""
     with Scope() as s:
         og = s.build(pl.flag_set(
             supp.channel("suppkey"), supp.n_rows,
@@ -606,12 +606,14 @@ def q11(supp: Page, ps: Page, n_part: int):
             [pl.ident(0), pl.ident(1)],
             preds=[pl.pred(1, CMP_GT, total_1e4 // 10000)]))
         fo.add_input_raw(groups)
-        out = fo.get_output(["partkey", "value_1e4"])
-        s.release(fo, jo, f, og, ok)
-    pk = out["partkey"]
-    val = out["value_1e4"] // 100  # exact: ticks are cents*100
-    order = np.lexsort((pk, -val))
-    return pk[order], val[order]
+        ob = s.run(OP_ORDER_BY, pl.order_by([pl.desc(1), pl.asc(0)], [0, 1]),
+                   fo.get_output_raw())
+        out = ob.get_output(["partkey", "value_1e4"])
+        s.release(ob, fo, jo, f, og, ok)
+    # ticks are cents*100, so the order of the ticks is the order of the
+    # cents and the division is exact
+    assert not (out["value_1e4"] % 100).any()
+    return out["partkey"], out["value_1e4"] // 100
 
 
 def q18(orders: Page, li: Page, limit=100):
@@ -1009,9 +1011,9 @@ def q16(part: Page, ps: Page, supp: Page, type_name):
 def q10(cust_n: int, orders: Page, li: Page, limit=20):
     """Q10 returned items (q10.sql): orders date filter fused into a
     chained build (payload custkey); returned lineitems emit-join to
-    their customer; per-customer revenue by fused-agg probe; bounded
-    top-`limit` (revenue desc, custkey asc) host-merged from the group
-    page.  Returns [(custkey, revenue_1e4)]."""
+    their customer; per-customer revenue by fused-agg probe; the group
+    page goes raw through rev > 0 into ORDER_BY (revenue desc, custkey
+    asc, limit).  Returns [(custkey, revenue_1e4)]."""
     with Scope() as s:
         odate = orders.channel("orderdate")
         oo = s.build(pl.hash_build(
@@ -1031,17 +1033,16 @@ def q10(cust_n: int, orders: Page, li: Page, limit=20):
             proj=pl.disc_price(li.channel("extendedprice"),
                                li.channel("discount")),
             dec_scale=4, dec_only=1), li)
-        g = j2.get_output(["custkey", "rev", "f64", "cnt"])
-        s.release(j2, oo, oc)
-    ck, rev = g["custkey"], g["rev"]
-    nz = rev > 0
-    ck, rev = ck[nz], rev[nz]
-    if len(rev) > limit:  # O(n) preselect, ties kept for the exact sort
-        kth = np.partition(rev, len(rev) - limit)[len(rev) - limit]
-        keep = rev >= kth
-        ck, rev = ck[keep], rev[keep]
-    top = np.lexsort((ck, -rev))[:limit]
-    return [(int(ck[i]), int(rev[i])) for i in top]
+        # [custkey, rev, f64, cnt] stays on the device: customers with
+        # revenue, sorted there, and only `limit` rows cross to the host
+        f, pos = s.pipe(OP_FILTER_PROJECT, pl.filter_project(
+            [pl.ident(0), pl.ident(1)], preds=[pl.pred(1, CMP_GT, 0)]),
+            j2.get_output_raw())
+        ob = s.run(OP_ORDER_BY, pl.order_by(
+            [pl.desc(1), pl.asc(0)], [0, 1], limit), pos)
+        top = ob.get_output(["custkey", "rev"])
+        s.release(ob, f, j2, oo, oc)
+    return [(int(c), int(r)) for c, r in zip(top["custkey"], top["rev"])]
 
 
 def q15(supp: Page, li: Page):

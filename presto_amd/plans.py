@@ -12,7 +12,9 @@ import ctypes as C
 
 from .engine import (
     Pred, Proj, Agg, PlanFilterProject, PlanHashAggSmall, PlanHashBuild,
-    PlanLookupJoin, PlanGroupBy, PlanTopN, PlanPartition,
+    PlanLookupJoin, PlanGroupBy, PlanTopN, PlanPartition, PlanOrderBy,
+    SORT_ASC_NULLS_FIRST, SORT_ASC_NULLS_LAST, SORT_DESC_NULLS_FIRST,
+    SORT_DESC_NULLS_LAST,
     CMP_CONTAINS2, CMP_NOT_CONTAINS2, CMP_IS_NULL, CMP_IS_NOT_NULL,
     JOIN_PROBE_OUTER, JOIN_LOOKUP_OUTER, JOIN_FULL_OUTER,
     PROJ_IDENT, PROJ_DISC_PRICE, PROJ_CHARGE, PROJ_MUL, PROJ_DIV,
@@ -260,6 +262,34 @@ def group_by(keys, aggs, capacity_hint, *, preds=(), filters=()):
 
 def top_n(limit, val_col, date_col, key_col):
     return PlanTopN(limit, val_col, date_col, key_col)
+
+
+def asc(col, nulls_last=True):
+    """ORDER BY key: col ASC NULLS LAST (or FIRST)."""
+    return (col, SORT_ASC_NULLS_LAST if nulls_last else SORT_ASC_NULLS_FIRST)
+
+
+def desc(col, nulls_last=True):
+    """ORDER BY key: col DESC NULLS LAST (or FIRST)."""
+    return (col,
+            SORT_DESC_NULLS_LAST if nulls_last else SORT_DESC_NULLS_FIRST)
+
+
+def order_by(keys, emit, limit=0):
+    """Stable multi-key sort: keys is a sequence of (col, order) pairs,
+    most significant first (see asc / desc); emit lists the output
+    channels; limit > 0 keeps the first `limit` rows."""
+    keys = list(keys)
+    p = PlanOrderBy()
+    p.n_keys = _fill(p.key_col, "key_col", [c for c, _ in keys])
+    _fill(p.order, "order", [o for _, o in keys])
+    p.n_emit = _fill(p.emit_cols, "emit_cols", emit)
+    if p.n_keys == 0:
+        raise ValueError("key_col: ORDER BY needs at least one key")
+    if p.n_emit == 0:
+        raise ValueError("emit_cols: ORDER BY needs at least one column")
+    p.limit = limit
+    return p
 
 
 def partition(n_partitions, key_col, emit):
