@@ -109,8 +109,11 @@ typedef struct {
                                  payloads, gathered probe-column masks,
                                  the drain page) and out of ORDER_BY
                                  (gathered masks of emitted columns, and
-                                 its keys honor theirs); every other
-                                 operator emits null_mask = NULL.  A mask follows
+                                 its keys honor theirs) and out of WINDOW
+                                 (the same, plus the masks of its SUM,
+                                 MIN, MAX, LAG and LEAD columns); every
+                                 other operator emits null_mask = NULL.
+                                 A mask follows
                                  its column: host for host columns,
                                  device for device columns.
                                  pg_page_serialize / pg_page_deserialize
@@ -280,6 +283,11 @@ typedef enum {
                                  PagesIndexOrdering + SortOrder.java; with
                                  a limit, the general TopNOperator (see
                                  pg_plan_order_by) */
+    /* 9 is left unassigned */
+    PG_OP_WINDOW = 10,        /* WindowOperator.java: ranking functions,
+                                 running and whole-partition aggregates,
+                                 LAG / LEAD over PARTITION BY ... ORDER BY
+                                 ... (see pg_plan_window) */
 } pg_op_kind;
 
 #define PG_MAX_PRED 8
@@ -643,6 +651,102 @@ typedef struct {
     int64_t limit;                     /* 0 = none; >0: first `limit` rows */
 } pg_plan_order_by;
 
+#define PG_MAX_WIN_FUNCS 8
+typedef enum { PG_WIN_ROW_NUMBER = 0, PG_WIN_RANK, PG_WIN_DENSE_RANK,
+               PG_WIN_COUNT, PG_WIN_SUM, PG_WIN_MIN, PG_WIN_MAX,
+               PG_WIN_LAG, PG_WIN_LEAD } pg_win_func;
+typedef enum { PG_FRAME_RANGE_RUNNING = 0, /* RANGE UNBOUNDED PRECEDING..CURRENT ROW (SQL default) */
+               PG_FRAME_ROWS_RUNNING  = 1, /* ROWS  UNBOUNDED PRECEDING..CURRENT ROW */
+               PG_FRAME_PARTITION     = 2  /* the whole partition */ } pg_win_frame;
+typedef struct { int32_t func;   /* pg_win_func */
+                 int32_t col;    /* argument channel (see per function) */
+                 int32_t frame;  /* pg_win_frame; aggregates only */
+                 int32_t pad;
+                 int64_t offset; /* LAG / LEAD: rows back / ahead, >= 0 */
+} pg_win_spec;
+
+typedef struct {
+    /* PG_OP_WINDOW: window functions over PARTITION BY ... ORDER BY ... of
+     * the accumulated pages, entirely on the GPU — WindowOperator.java with
+     * the functions of operator/window/ (RowNumberFunction, RankFunction,
+     * DenseRankFunction, LagFunction, LeadFunction, AggregateWindowFunction
+     * over count / sum / min / max).  The rows are sorted by ORDER_BY's
+     * sort; partition and peer-group boundaries, one segmented scan per
+     * aggregate and the per-function emit follow it.
+     *   - Lifecycle, page residency, key types, null ordering,
+     *     Double.compare order, emit columns and their gathered masks, the
+     *     0-row page, column typing from the first page and the 2^31-1 row
+     *     cap are exactly pg_plan_order_by's.  A finish that fails (SUM
+     *     overflow) leaves an operator whose every later add_input and
+     *     finish fail with the same error.
+     *   - Keys: the n_partition_keys partition keys first, then the order
+     *     keys; every key has a pg_sort_order, partition keys too.  Output
+     *     rows are the input rows stably sorted by all n_keys keys: ties
+     *     keep input order (page order, then row order).  This is STRICTER
+     *     than the reference and makes ROWS frames and ROW_NUMBER
+     *     deterministic.  With n_keys == 0 the input order is kept and
+     *     everything is one partition.
+     *   - Partitions and peers: two adjacent sorted rows are in the same
+     *     partition when they compare equal on the first n_partition_keys
+     *     keys under ORDER_BY's comparator, and are peers when they compare
+     *     equal on all keys.  So null equals null, every NaN equals every
+     *     NaN, and -0.0 DIFFERS from +0.0 — a deviation from the
+     *     reference, whose partition and peer tests use the types'
+     *     equalTo (under which the two zeros are equal).  With no order
+     *     keys every row of a partition is a peer of every other.
+     *   - Output: the n_emit emit columns first, then one column per
+     *     function, in plan order.
+     *   - ROW_NUMBER, RANK, DENSE_RANK: col, frame and offset are ignored.
+     *     I64, no mask.
+     *   - COUNT: col < 0 is count(*) over the frame; otherwise the
+     *     non-null rows of col, which may be of any fixed-width type.  I64,
+     *     no mask.
+     *   - SUM: over a U8, I32 or I64 col, nulls skipped, I64 output.  It
+     *     accumulates in 128 bits; finish fails with an error naming
+     *     WINDOW, SUM and the function index if any EMITTED value does not
+     *     fit int64.  For the two running frames that is exactly the
+     *     reference's Math.addExact behaviour.  For PG_FRAME_PARTITION it
+     *     is MORE LENIENT: the reference fails on an overflowing prefix
+     *     even when the partition's total fits.
+     *   - MIN / MAX: over a U8 (unsigned), I32 or I64 (signed) col, nulls
+     *     skipped; the output has the input type.
+     *   - Nulls of SUM, MIN, MAX: a frame with no non-null input gives
+     *     null.  These columns always carry a device null_mask; the value
+     *     under a null is 0.
+     *   - LAG / LEAD: col may be of any fixed-width type, I128 included,
+     *     and is copied bit for bit.  offset >= 0 counts rows in sorted
+     *     order within the partition; offset 0 is the row itself; frame is
+     *     ignored.  A target outside the partition gives null with value
+     *     0; otherwise the result is the target's value and its null flag.
+     *     These columns always carry a mask.
+     *   - Frames (aggregates): RANGE_RUNNING ends at the row's last peer,
+     *     ROWS_RUNNING at the row itself, PARTITION at the partition's
+     *     last row; all start at the partition's first row.
+     *   - Errors at create, naming the field: a count out of range,
+     *     n_partition_keys > n_keys, an unknown func, frame (aggregates) or
+     *     order, a negative offset (LAG / LEAD), a negative column where
+     *     one is required (keys, emit columns, every function argument but
+     *     COUNT's).  Errors at add_input, naming the function index and
+     *     column (or the key / emit entry, as ORDER_BY): an index >= n_cols,
+     *     a VARBIN or dictionary column anywhere, an I128 key, an I128 or
+     *     F64 column under SUM / MIN / MAX, a type that differs from the
+     *     first page's.  A rejected page leaves the operator as it was.
+     *   - Out of scope: F64 SUM, MIN and MAX (a parallel scan cannot
+     *     reproduce the reference's left-to-right rounding); bounded
+     *     frames (k PRECEDING, FOLLOWING); ntile, percent_rank, cume_dist,
+     *     first_value, last_value, nth_value; LAG / LEAD default values;
+     *     variable-width columns; a per-partition limit (compose ROW_NUMBER
+     *     with a downstream FILTER_PROJECT predicate instead); spilling. */
+    int32_t n_keys;             /* 0..4: partition keys first, then order keys */
+    int32_t n_partition_keys;   /* 0..n_keys */
+    int32_t key_col[PG_MAX_SORT_KEYS];
+    int32_t order[PG_MAX_SORT_KEYS];   /* pg_sort_order, for partition keys too */
+    int32_t n_emit;             /* 1..16 */
+    int32_t emit_cols[PG_MAX_SORT_EMIT];
+    int32_t n_funcs;            /* 1..8 */
+    pg_win_spec funcs[PG_MAX_WIN_FUNCS];
+} pg_plan_window;
+
 /* ---- operator lifecycle (Operator.java:20-102 analog) ---- */
 typedef int64_t pg_op;
 
@@ -703,8 +807,9 @@ pg_status pg_page_serialize(const pg_page* page /* host cols */,
  * pg_plan_partition}; returns how many it would fill.  Bindings compare
  * against their own struct sizes at load time. */
 int32_t pg_abi_struct_sizes(int32_t* out, int32_t n);
-/* sizeof the plan struct of an operator kind (all eight pg_op_kind values,
- * pg_plan_order_by included), or -1 for an unknown kind. */
+/* sizeof the plan struct of an operator kind (every pg_op_kind value,
+ * pg_plan_order_by and pg_plan_window included), or -1 for an unknown
+ * kind (the unassigned 9 among them). */
 int32_t pg_abi_plan_size(int32_t kind);
 /* the order-preserving key transform of PG_OP_ORDER_BY (csrc/sortkey.h,
  * the code k_sort_encode runs on the device): the u64 whose unsigned

@@ -30,5 +30,9 @@ from .engine import (  # noqa: F401
     OP_TOPN, OP_PARTITION, OP_GROUPBY_MULTI, OP_ORDER_BY,
     PlanOrderBy, SORT_ASC_NULLS_FIRST, SORT_ASC_NULLS_LAST,
     SORT_DESC_NULLS_FIRST, SORT_DESC_NULLS_LAST,
+    OP_WINDOW, PlanWindow, WinSpec,
+    WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_COUNT, WIN_SUM, WIN_MIN,
+    WIN_MAX, WIN_LAG, WIN_LEAD,
+    FRAME_RANGE_RUNNING, FRAME_ROWS_RUNNING, FRAME_PARTITION,
 )
 from . import pipelines, plans  # noqa: F401

@@ -3586,6 +3586,498 @@ __global__ __launch_bounds__(256) void k_sort_gather(const uint32_t* rowid,
     }
 }
 
+/* ids[i] = i: the "sorted" permutation of a plan without keys */
+__global__ __launch_bounds__(256) void k_sort_iota(uint32_t* ids, int64_t n)
+{
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n;
+         i += stride)
+        ids[i] = (uint32_t)i;
+}
+
+/* ------------------------------------------------------------------ */
+/* WINDOW — WindowOperator.java over the sorted PagesIndex: what runs */
+/* after the sort.  Boundary flags from the keys of adjacent sorted   */
+/* rows, per-row partition / peer-group bounds from scans of the head */
+/* indices, one segmented scan per aggregate, and a per-function emit */
+/* that reads those at the row, at its peer group's end or at its     */
+/* partition's end.                                                   */
+/*                                                                    */
+/* Every scan is three launches in the sort's chunk geometry: each    */
+/* block folds its chunk into a carry, one block scans the <= SORT_NB */
+/* carries, each block rescans its chunk from its carry-in.  No block */
+/* ever waits on another.                                             */
+/* ------------------------------------------------------------------ */
+#define WIN_PART_HEAD 1 /* first row of a partition */
+#define WIN_PEER_HEAD 2 /* first row of a peer group */
+#define WIN_NONE 0xffffffffu /* no head: above every row index */
+
+/* inclusive scan over the block's 256 threads of a type with
+ * identity / combine / shfl_up: wave64 shuffles, then the four wave
+ * totals through LDS.  excl is the scan without the thread's own value,
+ * total the fold of all 256.  Every thread of the block must call it. */
+template <class T>
+__device__ inline T win_scan256(T v, T* wtot, T& excl, T& total)
+{
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        T o = T::shfl_up(v, d);
+        if (lane >= d) v = T::combine(o, v);
+    }
+    T up = T::shfl_up(v, 1);
+    if (lane == 0) up = T::identity();
+    if (lane == 63) wtot[wid] = v;
+    __syncthreads();
+    T pre = T::identity(), tot = T::identity();
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        T t = wtot[w];
+        if (w < wid) pre = T::combine(pre, t);
+        tot = T::combine(tot, t);
+    }
+    __syncthreads(); /* wtot is free for the next call */
+    total = tot;
+    excl = T::combine(pre, up);
+    return T::combine(pre, v);
+}
+
+/* exclusive scan, in place, of nb <= SORT_NB block carries by one block:
+ * each thread folds its run of consecutive carries, the 256 partial folds
+ * are scanned, and the thread rewrites its run.  REV scans from the last
+ * carry down (for a commutative combine only). */
+template <class T, bool REV>
+__device__ inline void win_carry_scan(T* c, int nb, T* wtot)
+{
+    const int per = (nb + 255) / 256;
+    const int lo = min((int)threadIdx.x * per, nb);
+    const int hi = min(lo + per, nb);
+    T s = T::identity();
+    for (int k = lo; k < hi; k++)
+        s = T::combine(s, c[REV ? nb - 1 - k : k]);
+    T run, tot;
+    win_scan256(s, wtot, run, tot);
+    for (int k = lo; k < hi; k++) {
+        const int j = REV ? nb - 1 - k : k;
+        T cur = c[j];
+        c[j] = run;
+        run = T::combine(run, cur);
+    }
+}
+
+/* forward: the last partition head and the last peer head at or before a
+ * row (-1: none yet) and the number of peer heads up to it */
+struct win_fwd {
+    int32_t part, peer;
+    uint32_t heads;
+    static __device__ inline win_fwd identity() { return {-1, -1, 0}; }
+    static __device__ inline win_fwd combine(win_fwd a, win_fwd b)
+    {
+        return {max(a.part, b.part), max(a.peer, b.peer), a.heads + b.heads};
+    }
+    static __device__ inline win_fwd shfl_up(win_fwd v, int d)
+    {
+        return {__shfl_up(v.part, d, 64), __shfl_up(v.peer, d, 64),
+                __shfl_up(v.heads, d, 64)};
+    }
+};
+/* backward: the first partition head and the first peer head after a row */
+struct win_bwd {
+    uint32_t part, peer;
+    static __device__ inline win_bwd identity()
+    {
+        return {WIN_NONE, WIN_NONE};
+    }
+    static __device__ inline win_bwd combine(win_bwd a, win_bwd b)
+    {
+        return {min(a.part, b.part), min(a.peer, b.peer)};
+    }
+    static __device__ inline win_bwd shfl_up(win_bwd v, int d)
+    {
+        return {__shfl_up(v.part, d, 64), __shfl_up(v.peer, d, 64)};
+    }
+};
+
+struct win_keys {
+    int n_keys, n_part;
+    const void* col[PG_MAX_SORT_KEYS];
+    const uint8_t* mask[PG_MAX_SORT_KEYS]; /* NULL: the key has no nulls */
+    int tag[PG_MAX_SORT_KEYS];
+};
+
+/* do input rows a and b differ on key j under ORDER_BY's comparator:
+ * null equals null, and pg_sortkey maps every NaN to one key */
+__device__ inline bool win_key_differs(const win_keys& k, int j, uint32_t a,
+                                       uint32_t b)
+{
+    const bool na = k.mask[j] && k.mask[j][a];
+    const bool nb = k.mask[j] && k.mask[j][b];
+    if (na || nb) return na != nb;
+    uint64_t x, y;
+    switch (k.tag[j]) {
+        case PG_T_U8:
+            x = ((const uint8_t*)k.col[j])[a];
+            y = ((const uint8_t*)k.col[j])[b];
+            break;
+        case PG_T_I32:
+            x = ((const uint32_t*)k.col[j])[a];
+            y = ((const uint32_t*)k.col[j])[b];
+            break;
+        default:
+            x = ((const uint64_t*)k.col[j])[a];
+            y = ((const uint64_t*)k.col[j])[b];
+            break;
+    }
+    return pg_sortkey(k.tag[j], 0, x) != pg_sortkey(k.tag[j], 0, y);
+}
+
+/* launch 1 of the bounds scans, fused with the flags: sorted row i
+ * against row i-1, key by key; a difference on a partition key heads a
+ * partition (and a peer group), one on an order key a peer group.  The
+ * block's carries: its last / first heads and its peer-head count. */
+__global__ __launch_bounds__(256) void k_win_flags(
+    win_keys k, const uint32_t* ids, int64_t n, int64_t chunk,
+    uint8_t* flags, win_fwd* fwdc, win_bwd* bwdc)
+{
+    __shared__ win_fwd wf[4];
+    __shared__ win_bwd wb[4];
+    const int64_t lo = (int64_t)blockIdx.x * chunk;
+    const int64_t hi = min(lo + chunk, n);
+    win_fwd f = win_fwd::identity();
+    win_bwd b = win_bwd::identity();
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+        uint8_t fl = 0;
+        if (i == 0) {
+            fl = WIN_PART_HEAD | WIN_PEER_HEAD;
+        } else {
+            const uint32_t r = ids[i], p = ids[i - 1];
+            for (int j = 0; j < k.n_keys; j++)
+                if (win_key_differs(k, j, r, p)) {
+                    fl = j < k.n_part ? WIN_PART_HEAD | WIN_PEER_HEAD
+                                      : WIN_PEER_HEAD;
+                    break;
+                }
+        }
+        flags[i] = fl;
+        if (fl & WIN_PART_HEAD) {
+            f.part = max(f.part, (int32_t)i);
+            b.part = min(b.part, (uint32_t)i);
+        }
+        if (fl & WIN_PEER_HEAD) {
+            f.peer = max(f.peer, (int32_t)i);
+            b.peer = min(b.peer, (uint32_t)i);
+            f.heads++;
+        }
+    }
+    /* both combines commute, so the strided per-thread folds are fine */
+    win_fwd xf, tf;
+    win_bwd xb, tb;
+    win_scan256(f, wf, xf, tf);
+    win_scan256(b, wb, xb, tb);
+    if (threadIdx.x == 0) {
+        fwdc[blockIdx.x] = tf;
+        bwdc[blockIdx.x] = tb;
+    }
+}
+
+/* launch 2: block b's carry-in = the fold of the blocks before it
+ * (forward) and after it (backward) */
+__global__ __launch_bounds__(256) void k_win_bounds_carry(win_fwd* fwdc,
+                                                          win_bwd* bwdc,
+                                                          int nb)
+{
+    __shared__ win_fwd wf[4];
+    __shared__ win_bwd wb[4];
+    win_carry_scan<win_fwd, false>(fwdc, nb, wf);
+    win_carry_scan<win_bwd, true>(bwdc, nb, wb);
+}
+
+/* launch 3: per row, the first row of its partition and of its peer
+ * group and the running count of peer heads (a forward scan), then the
+ * last row of its peer group and of its partition (a backward scan: the
+ * element of row i is the head bit of row i+1) */
+__global__ __launch_bounds__(256) void k_win_bounds(
+    const uint8_t* flags, int64_t n, int64_t chunk, const win_fwd* fwdc,
+    const win_bwd* bwdc, uint32_t* part_start, uint32_t* peer_start,
+    uint32_t* heads, uint32_t* part_end, uint32_t* peer_end)
+{
+    __shared__ win_fwd wf[4];
+    __shared__ win_bwd wb[4];
+    const int64_t lo = (int64_t)blockIdx.x * chunk;
+    const int64_t hi = min(lo + chunk, n);
+    win_fwd frun = fwdc[blockIdx.x];
+    for (int64_t base = lo; base < hi; base += SORT_WINDOW) {
+        const int64_t i = base + threadIdx.x;
+        const bool valid = i < hi;
+        const uint8_t fl = valid ? flags[i] : 0;
+        win_fwd e = {fl & WIN_PART_HEAD ? (int32_t)i : -1,
+                     fl & WIN_PEER_HEAD ? (int32_t)i : -1,
+                     fl & WIN_PEER_HEAD ? 1u : 0u};
+        win_fwd ex, tot;
+        e = win_fwd::combine(frun, win_scan256(e, wf, ex, tot));
+        if (valid) {
+            /* row 0 heads both, so neither index is -1 here */
+            part_start[i] = (uint32_t)e.part;
+            peer_start[i] = (uint32_t)e.peer;
+            heads[i] = e.heads;
+        }
+        frun = win_fwd::combine(frun, tot);
+    }
+    win_bwd brun = bwdc[blockIdx.x];
+    for (int64_t base = hi - 1; base >= lo; base -= SORT_WINDOW) {
+        const int64_t i = base - threadIdx.x;
+        const bool valid = i >= lo;
+        /* heads at or past hi are in the carry-in */
+        const uint8_t fl = valid && i + 1 < hi ? flags[i + 1] : 0;
+        win_bwd e = {fl & WIN_PART_HEAD ? (uint32_t)(i + 1) : WIN_NONE,
+                     fl & WIN_PEER_HEAD ? (uint32_t)(i + 1) : WIN_NONE};
+        win_bwd ex, tot;
+        e = win_bwd::combine(brun, win_scan256(e, wb, ex, tot));
+        if (valid) {
+            part_end[i] = (e.part == WIN_NONE ? (uint32_t)n : e.part) - 1;
+            peer_end[i] = (e.peer == WIN_NONE ? (uint32_t)n : e.peer) - 1;
+        }
+        brun = win_bwd::combine(brun, tot);
+    }
+}
+
+/* the scanned state of one aggregate: the non-null count, the 128-bit
+ * sum (SUM: hi:lo, two's complement) or the extreme (MIN / MAX: lo as a
+ * signed 64-bit value), and whether a partition head has been passed —
+ * the segmented scan's reset bit.  K is the pg_win_func. */
+template <int K>
+struct win_acc {
+    uint64_t lo;
+    int64_t hi;
+    uint32_t cnt;
+    uint32_t head;
+    static __device__ inline win_acc identity()
+    {
+        return {K == PG_WIN_MIN   ? (uint64_t)INT64_MAX
+                : K == PG_WIN_MAX ? (uint64_t)INT64_MIN
+                                  : 0,
+                0, 0, 0};
+    }
+    /* a then b, b later in sorted order */
+    static __device__ inline win_acc combine(win_acc a, win_acc b)
+    {
+        if (b.head) return b;
+        win_acc r = b;
+        r.head = a.head;
+        r.cnt = a.cnt + b.cnt;
+        if (K == PG_WIN_SUM) {
+            uint64_t h = (uint64_t)b.hi;
+            r.lo = b.lo;
+            fx128_add(&h, &r.lo, (uint64_t)a.hi, a.lo);
+            r.hi = (int64_t)h;
+        } else if (K == PG_WIN_MIN) {
+            r.lo = (uint64_t)min((int64_t)a.lo, (int64_t)b.lo);
+        } else if (K == PG_WIN_MAX) {
+            r.lo = (uint64_t)max((int64_t)a.lo, (int64_t)b.lo);
+        }
+        return r;
+    }
+    static __device__ inline win_acc shfl_up(win_acc v, int d)
+    {
+        win_acc r = v;
+        if (K != PG_WIN_COUNT)
+            r.lo = (uint64_t)__shfl_up((long long)v.lo, d, 64);
+        if (K == PG_WIN_SUM) r.hi = __shfl_up((long long)v.hi, d, 64);
+        r.cnt = __shfl_up(v.cnt, d, 64);
+        r.head = __shfl_up(v.head, d, 64);
+        return r;
+    }
+};
+
+struct win_arg {
+    const void* col;     /* NULL: count(*) */
+    const uint8_t* mask; /* NULL: no nulls */
+    int tag;
+};
+
+/* sorted row i as a scan element: the argument gathered through ids, a
+ * null as the identity */
+template <int K>
+__device__ inline win_acc<K> win_load(const win_arg& a, const uint32_t* ids,
+                                      const uint8_t* flags, int64_t i)
+{
+    win_acc<K> e = win_acc<K>::identity();
+    e.head = flags[i] & WIN_PART_HEAD;
+    if (K == PG_WIN_COUNT && !a.mask) {
+        e.cnt = 1;
+        return e;
+    }
+    const uint32_t r = ids[i];
+    if (a.mask && a.mask[r]) return e;
+    e.cnt = 1;
+    if (K != PG_WIN_COUNT) {
+        int64_t v;
+        switch (a.tag) {
+            case PG_T_U8: v = ((const uint8_t*)a.col)[r]; break;
+            case PG_T_I32: v = ((const int32_t*)a.col)[r]; break;
+            default: v = ((const int64_t*)a.col)[r]; break;
+        }
+        e.lo = (uint64_t)v;
+        e.hi = v < 0 ? -1 : 0;
+    }
+    return e;
+}
+
+/* launch 1 of an aggregate's scan: the block's chunk folded in row order
+ * (the segmented combine does not commute) */
+template <int K>
+__global__ __launch_bounds__(256) void k_win_agg_reduce(
+    win_arg a, const uint32_t* ids, const uint8_t* flags, int64_t n,
+    int64_t chunk, win_acc<K>* carry)
+{
+    __shared__ win_acc<K> wtot[4];
+    const int64_t lo = (int64_t)blockIdx.x * chunk;
+    const int64_t hi = min(lo + chunk, n);
+    win_acc<K> run = win_acc<K>::identity();
+    for (int64_t base = lo; base < hi; base += SORT_WINDOW) {
+        const int64_t i = base + threadIdx.x;
+        win_acc<K> e = i < hi ? win_load<K>(a, ids, flags, i)
+                              : win_acc<K>::identity();
+        win_acc<K> ex, tot;
+        win_scan256(e, wtot, ex, tot);
+        run = win_acc<K>::combine(run, tot);
+    }
+    if (threadIdx.x == 0) carry[blockIdx.x] = run;
+}
+
+/* launch 2 */
+template <int K>
+__global__ __launch_bounds__(256) void k_win_agg_carry(win_acc<K>* carry,
+                                                       int nb)
+{
+    __shared__ win_acc<K> wtot[4];
+    win_carry_scan<win_acc<K>, false>(carry, nb, wtot);
+}
+
+/* launch 3: the inclusive segmented scan, written per sorted row */
+template <int K>
+__global__ __launch_bounds__(256) void k_win_agg_scan(
+    win_arg a, const uint32_t* ids, const uint8_t* flags, int64_t n,
+    int64_t chunk, const win_acc<K>* carry, uint64_t* s_lo, int64_t* s_hi,
+    uint32_t* s_cnt)
+{
+    __shared__ win_acc<K> wtot[4];
+    const int64_t lo = (int64_t)blockIdx.x * chunk;
+    const int64_t hi = min(lo + chunk, n);
+    win_acc<K> run = carry[blockIdx.x];
+    for (int64_t base = lo; base < hi; base += SORT_WINDOW) {
+        const int64_t i = base + threadIdx.x;
+        const bool valid = i < hi;
+        win_acc<K> e = valid ? win_load<K>(a, ids, flags, i)
+                             : win_acc<K>::identity();
+        win_acc<K> ex, tot;
+        e = win_acc<K>::combine(run, win_scan256(e, wtot, ex, tot));
+        if (valid) {
+            s_cnt[i] = e.cnt;
+            if (K != PG_WIN_COUNT) s_lo[i] = e.lo;
+            if (K == PG_WIN_SUM) s_hi[i] = e.hi;
+        }
+        run = win_acc<K>::combine(run, tot);
+    }
+}
+
+/* one function's output column (and mask) from the bounds and, for the
+ * aggregates, from the scan read at the frame's last row */
+struct win_emit {
+    int func, frame, width; /* width: bytes of an output value */
+    int64_t offset;
+    const uint32_t *ids, *part_start, *peer_start, *heads, *part_end,
+        *peer_end;
+    const uint64_t* s_lo;
+    const int64_t* s_hi;
+    const uint32_t* s_cnt;
+    const void* col;      /* LAG / LEAD: the column and its mask */
+    const uint8_t* cmask;
+    void* out;
+    uint8_t* omask; /* NULL for the columns that are never null */
+    int32_t* err;   /* set to 1 by a SUM outside int64 */
+};
+
+__device__ inline void win_store(void* out, int width, int64_t i, int64_t v)
+{
+    switch (width) {
+        case 1: ((uint8_t*)out)[i] = (uint8_t)v; break;
+        case 4: ((int32_t*)out)[i] = (int32_t)v; break;
+        default: ((int64_t*)out)[i] = v; break;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_win_emit(win_emit e, int64_t n)
+{
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n;
+         i += stride) {
+        switch (e.func) {
+            case PG_WIN_ROW_NUMBER:
+                ((int64_t*)e.out)[i] = i - e.part_start[i] + 1;
+                break;
+            case PG_WIN_RANK:
+                ((int64_t*)e.out)[i] =
+                    (int64_t)e.peer_start[i] - e.part_start[i] + 1;
+                break;
+            case PG_WIN_DENSE_RANK:
+                ((int64_t*)e.out)[i] =
+                    (int64_t)e.heads[i] - e.heads[e.part_start[i]] + 1;
+                break;
+            case PG_WIN_LAG:
+            case PG_WIN_LEAD: {
+                int64_t t = -1;
+                if (e.func == PG_WIN_LAG) {
+                    if (e.offset <= i - (int64_t)e.part_start[i])
+                        t = i - e.offset;
+                } else if (e.offset <= (int64_t)e.part_end[i] - i) {
+                    t = i + e.offset;
+                }
+                const uint32_t r = t < 0 ? 0 : e.ids[t];
+                const bool null = t < 0 || (e.cmask && e.cmask[r]);
+                if (e.width == 16) {
+                    ulonglong2 v = {0, 0};
+                    if (t >= 0) v = ((const ulonglong2*)e.col)[r];
+                    ((ulonglong2*)e.out)[i] = v;
+                } else {
+                    int64_t v = 0;
+                    if (t >= 0) switch (e.width) {
+                        case 1: v = ((const uint8_t*)e.col)[r]; break;
+                        case 4: v = ((const int32_t*)e.col)[r]; break;
+                        default: v = ((const int64_t*)e.col)[r]; break;
+                    }
+                    win_store(e.out, e.width, i, v);
+                }
+                e.omask[i] = null;
+                break;
+            }
+            default: {
+                const int64_t at = e.frame == PG_FRAME_ROWS_RUNNING ? i
+                                   : e.frame == PG_FRAME_RANGE_RUNNING
+                                       ? (int64_t)e.peer_end[i]
+                                       : (int64_t)e.part_end[i];
+                const uint32_t cnt = e.s_cnt[at];
+                if (e.func == PG_WIN_COUNT) {
+                    ((int64_t*)e.out)[i] = cnt;
+                    break;
+                }
+                int64_t v = 0;
+                if (cnt) {
+                    v = (int64_t)e.s_lo[at];
+                    /* fits int64: the high word is the sign extension */
+                    if (e.func == PG_WIN_SUM && e.s_hi[at] != (v >> 63)) {
+                        *e.err = 1;
+                        v = 0;
+                    }
+                }
+                win_store(e.out, e.width, i, v);
+                e.omask[i] = cnt == 0;
+                break;
+            }
+        }
+    }
+}
+
 /* ================================================================== */
 /* host side: operator state machines + C-ABI                         */
 /* ================================================================== */
@@ -5932,11 +6424,28 @@ struct PartitionOp : Op {
     }
 };
 
-/* ---------------- ORDER_BY ---------------- */
-struct OrderByOp : Op {
-    pg_plan_order_by plan;
+/* the sort's block geometry, shared by the scans of WINDOW: a block owns
+ * a chunk of whole SORT_WINDOW-row windows, at most SORT_NB blocks */
+static int sort_geometry(int64_t n, int64_t* chunk_out)
+{
+    int64_t chunk = (n + SORT_NB - 1) / SORT_NB;
+    chunk = (chunk + SORT_WINDOW - 1) / SORT_WINDOW * SORT_WINDOW;
+    chunk = std::max<int64_t>(chunk, SORT_MIN_WINDOWS * SORT_WINDOW);
+    *chunk_out = chunk;
+    return (int)((n + chunk - 1) / chunk);
+}
+
+/* ---------------- what ORDER_BY and WINDOW share ---------------- */
+/* page accumulation into per-column slots, their concatenation, the
+ * sorted row-id permutation and the gather of the emit columns.  The
+ * operator sets opname, the key list and the emit list from its plan. */
+struct SortedInputOp : Op {
+    const char* opname = ""; /* "ORDER_BY" / "WINDOW": prefixes errors */
+    int n_keys = 0, n_emit = 0;
+    const int32_t *key_col = nullptr, *order = nullptr, *emit_cols = nullptr;
     /* one slot per distinct input column the plan names, as key, as emit
-     * column or both: the per-page copies, then the concatenation */
+     * column, as function argument or several of these: the per-page
+     * copies, then the concatenation */
     struct Slot {
         int col = 0;
         int tag = PG_T_I64; /* the first page's; I64 until one is fed */
@@ -5951,10 +6460,13 @@ struct OrderByOp : Op {
     int64_t n_total = 0;
     bool typed = false;
 
-    static std::string fname(const char* field, int i)
+    std::string err(const std::string& what) const
     {
-        return std::string("ORDER_BY: ") + field + "[" + std::to_string(i) +
-               "]";
+        return std::string(opname) + ": " + what;
+    }
+    std::string fname(const char* field, int i) const
+    {
+        return err(field) + "[" + std::to_string(i) + "]";
     }
     int slot_of(int col)
     {
@@ -5964,32 +6476,29 @@ struct OrderByOp : Op {
         slots.back().col = col;
         return (int)slots.size() - 1;
     }
-    void init()
+    /* after the operator has checked its counts: the per-entry checks of
+     * the key and emit lists, and their slots */
+    void init_keys_and_emit()
     {
-        if (plan.n_keys < 1 || plan.n_keys > PG_MAX_SORT_KEYS)
-            throw std::runtime_error("ORDER_BY: n_keys must be 1..4");
-        if (plan.n_emit < 1 || plan.n_emit > PG_MAX_SORT_EMIT)
-            throw std::runtime_error("ORDER_BY: n_emit must be 1..16");
-        if (plan.limit < 0)
-            throw std::runtime_error("ORDER_BY: limit must be >= 0");
-        for (int i = 0; i < plan.n_keys; i++) {
-            if (plan.order[i] < PG_SORT_ASC_NULLS_FIRST ||
-                plan.order[i] > PG_SORT_DESC_NULLS_LAST)
+        for (int i = 0; i < n_keys; i++) {
+            if (order[i] < PG_SORT_ASC_NULLS_FIRST ||
+                order[i] > PG_SORT_DESC_NULLS_LAST)
                 throw std::runtime_error(fname("order", i) +
                                          " is not a pg_sort_order");
-            if (plan.key_col[i] < 0)
+            if (key_col[i] < 0)
                 throw std::runtime_error(fname("key_col", i) +
                                          " is negative");
         }
-        for (int i = 0; i < plan.n_emit; i++)
-            if (plan.emit_cols[i] < 0)
+        for (int i = 0; i < n_emit; i++)
+            if (emit_cols[i] < 0)
                 throw std::runtime_error(fname("emit_cols", i) +
                                          " is negative");
-        for (int i = 0; i < plan.n_keys; i++)
-            key_slot[i] = slot_of(plan.key_col[i]);
-        for (int i = 0; i < plan.n_emit; i++)
-            emit_slot[i] = slot_of(plan.emit_cols[i]);
+        for (int i = 0; i < n_keys; i++) key_slot[i] = slot_of(key_col[i]);
+        for (int i = 0; i < n_emit; i++)
+            emit_slot[i] = slot_of(emit_cols[i]);
     }
+    /* the operator's own per-page checks, beyond keys and emit columns */
+    virtual void check_more(const pg_page*) {}
     void check_col(const pg_page* in, const std::string& name, int c,
                    bool is_key)
     {
@@ -6018,15 +6527,16 @@ struct OrderByOp : Op {
     {
         /* every check before the first copy: a rejected page leaves the
          * operator as it was */
-        if (in->n_rows < 0) throw std::runtime_error("ORDER_BY: n_rows < 0");
-        for (int i = 0; i < plan.n_keys; i++)
-            check_col(in, fname("key_col", i), plan.key_col[i], true);
-        for (int i = 0; i < plan.n_emit; i++)
-            check_col(in, fname("emit_cols", i), plan.emit_cols[i], false);
+        if (in->n_rows < 0) throw std::runtime_error(err("n_rows < 0"));
+        for (int i = 0; i < n_keys; i++)
+            check_col(in, fname("key_col", i), key_col[i], true);
+        for (int i = 0; i < n_emit; i++)
+            check_col(in, fname("emit_cols", i), emit_cols[i], false);
+        check_more(in);
         const int64_t n = in->n_rows;
         if (n_total + n > INT32_MAX)
-            throw std::runtime_error("ORDER_BY: more than 2^31-1 accumulated "
-                                     "rows (row ids are 32-bit)");
+            throw std::runtime_error(err("more than 2^31-1 accumulated "
+                                         "rows (row ids are 32-bit)"));
         for (auto& s : slots) {
             const pg_col& col = in->cols[s.col];
             s.tag = col.tag;
@@ -6090,21 +6600,29 @@ struct OrderByOp : Op {
         s.data.clear();
         s.mask.clear();
     }
-    /* the sorted permutation of [0, n) for n >= 2: a fixed launch
-     * sequence on g_stream with one host read (the digit histograms) per
-     * key.  Returns which of the two id buffers holds it. */
-    uint32_t* sort_ids(int64_t n, DevBuf& idA, DevBuf& idB)
+    /* the sorted permutation of [0, n): a fixed launch sequence on
+     * g_stream with one host read (the digit histograms) per key.
+     * Allocates the id buffers it needs and returns which of the two
+     * holds the result: NULL for no rows, the identity for one row or no
+     * keys. */
+    const uint32_t* sort_ids(int64_t n, DevBuf& idA, DevBuf& idB)
     {
+        if (n == 0) return nullptr;
+        idA.alloc((size_t)n * 4);
+        const int sgrid = (int)std::min<int64_t>((n + 255) / 256, 2048);
+        if (n == 1 || n_keys == 0) {
+            hipLaunchKernelGGL(k_sort_iota, dim3(sgrid), dim3(256), 0,
+                               g_stream, (uint32_t*)idA.p, n);
+            return (const uint32_t*)idA.p;
+        }
+        idB.alloc((size_t)n * 4);
         DevBuf kA, kB, hist, counts;
         kA.alloc((size_t)n * 8);
         kB.alloc((size_t)n * 8);
         hist.alloc(8 * 256 * 4);
-        int64_t chunk = (n + SORT_NB - 1) / SORT_NB;
-        chunk = (chunk + SORT_WINDOW - 1) / SORT_WINDOW * SORT_WINDOW;
-        chunk = std::max<int64_t>(chunk, SORT_MIN_WINDOWS * SORT_WINDOW);
-        const int nb = (int)((n + chunk - 1) / chunk);
+        int64_t chunk;
+        const int nb = sort_geometry(n, &chunk);
         counts.alloc((size_t)256 * nb * 4);
-        const int sgrid = (int)std::min<int64_t>((n + 255) / 256, 2048);
         uint64_t *kin = (uint64_t*)kA.p, *kout = (uint64_t*)kB.p;
         uint32_t *iin = (uint32_t*)idA.p, *iout = (uint32_t*)idB.p;
         /* one pass over digit `shift / 8`; hist holds the histograms of
@@ -6123,14 +6641,14 @@ struct OrderByOp : Op {
             std::swap(iin, iout);
         };
         std::vector<uint32_t> h(8 * 256);
-        for (int k = plan.n_keys - 1; k >= 0; k--) {
+        for (int k = n_keys - 1; k >= 0; k--) {
             const Slot& s = slots[key_slot[k]];
             const uint8_t* mask =
                 s.has_mask ? (const uint8_t*)s.all_mask.p : nullptr;
-            const bool first = k == plan.n_keys - 1;
+            const bool first = k == n_keys - 1;
             hipLaunchKernelGGL(k_sort_encode, dim3(sgrid), dim3(256), 0,
                                g_stream, (const void*)s.all.p, s.tag,
-                               plan.order[k], mask, 0,
+                               order[k], mask, 0,
                                first ? (const uint32_t*)nullptr : iin, iin,
                                kin, n);
             hist.zero();
@@ -6151,7 +6669,7 @@ struct OrderByOp : Op {
                  * bins over the gathered mask byte */
                 hipLaunchKernelGGL(k_sort_encode, dim3(sgrid), dim3(256), 0,
                                    g_stream, (const void*)s.all.p, s.tag,
-                                   plan.order[k], mask, 1,
+                                   order[k], mask, 1,
                                    (const uint32_t*)iin, iin, kin, n);
                 hist.zero();
                 hipLaunchKernelGGL(k_sort_digits, dim3(sgrid), dim3(256), 0,
@@ -6162,28 +6680,14 @@ struct OrderByOp : Op {
         CHKV(hipStreamSynchronize(g_stream)); /* before kA/kB are pooled */
         return iin;
     }
-    void finish() override
+    /* the emit columns of the first n_out sorted rows into columns
+     * [0, n_emit) of the output page, each with its gathered mask if it
+     * has one */
+    void gather_emit(OutPage& op, const uint32_t* ids, int64_t n_out)
     {
-        const int64_t n = n_total;
-        for (auto& s : slots) concat(s);
-        DevBuf idA, idB;
-        const uint32_t* ids = nullptr;
-        if (n >= 2) {
-            idA.alloc((size_t)n * 4);
-            idB.alloc((size_t)n * 4);
-            ids = sort_ids(n, idA, idB);
-        } else if (n == 1) {
-            idA.alloc(4);
-            idA.zero(); /* the one row is row 0 */
-            ids = (const uint32_t*)idA.p;
-        }
-        const int64_t n_out = plan.limit > 0 ? std::min(plan.limit, n) : n;
-        OutPage op;
-        op.pg.n_rows = n_out;
-        op.pg.n_cols = plan.n_emit;
         sort_gather_cols g{};
-        g.n = plan.n_emit;
-        for (int o = 0; o < plan.n_emit; o++) {
+        g.n = n_emit;
+        for (int o = 0; o < n_emit; o++) {
             const Slot& s = slots[emit_slot[o]];
             const size_t w = type_size(s.tag);
             op.dev.emplace_back();
@@ -6209,11 +6713,302 @@ struct OrderByOp : Op {
             hipLaunchKernelGGL(k_sort_gather, dim3(grid), dim3(256), 0,
                                g_stream, ids, n_out, g);
         }
-        CHKV(hipStreamSynchronize(g_stream));
+    }
+    void free_slots()
+    {
         for (auto& s : slots) {
             s.all.free();
             s.all_mask.free();
         }
+    }
+};
+
+/* ---------------- ORDER_BY ---------------- */
+struct OrderByOp : SortedInputOp {
+    pg_plan_order_by plan;
+    void init()
+    {
+        opname = "ORDER_BY";
+        if (plan.n_keys < 1 || plan.n_keys > PG_MAX_SORT_KEYS)
+            throw std::runtime_error("ORDER_BY: n_keys must be 1..4");
+        if (plan.n_emit < 1 || plan.n_emit > PG_MAX_SORT_EMIT)
+            throw std::runtime_error("ORDER_BY: n_emit must be 1..16");
+        if (plan.limit < 0)
+            throw std::runtime_error("ORDER_BY: limit must be >= 0");
+        n_keys = plan.n_keys;
+        key_col = plan.key_col;
+        order = plan.order;
+        n_emit = plan.n_emit;
+        emit_cols = plan.emit_cols;
+        init_keys_and_emit();
+    }
+    void finish() override
+    {
+        const int64_t n = n_total;
+        for (auto& s : slots) concat(s);
+        DevBuf idA, idB;
+        const uint32_t* ids = sort_ids(n, idA, idB);
+        const int64_t n_out = plan.limit > 0 ? std::min(plan.limit, n) : n;
+        OutPage op;
+        op.pg.n_rows = n_out;
+        op.pg.n_cols = plan.n_emit;
+        gather_emit(op, ids, n_out);
+        CHKV(hipStreamSynchronize(g_stream));
+        free_slots();
+        outq.push_back(std::move(op));
+    }
+};
+
+/* ---------------- WINDOW ---------------- */
+struct WindowOp : SortedInputOp {
+    pg_plan_window plan;
+    int arg_slot[PG_MAX_WIN_FUNCS]; /* -1: the function reads no column */
+    std::string failed; /* a finish that failed fails again, the same way */
+
+    static const char* func_name(int f)
+    {
+        static const char* const names[] = {
+            "ROW_NUMBER", "RANK", "DENSE_RANK", "COUNT", "SUM",
+            "MIN",        "MAX",  "LAG",        "LEAD"};
+        return names[f];
+    }
+    static bool is_agg(int f) { return f >= PG_WIN_COUNT && f <= PG_WIN_MAX; }
+    static bool is_shift(int f) { return f == PG_WIN_LAG || f == PG_WIN_LEAD; }
+    std::string fn(int i, const char* field) const
+    {
+        return fname("funcs", i) + "." + field;
+    }
+    void init()
+    {
+        opname = "WINDOW";
+        if (plan.n_keys < 0 || plan.n_keys > PG_MAX_SORT_KEYS)
+            throw std::runtime_error("WINDOW: n_keys must be 0..4");
+        if (plan.n_partition_keys < 0 || plan.n_partition_keys > plan.n_keys)
+            throw std::runtime_error(
+                "WINDOW: n_partition_keys must be 0..n_keys");
+        if (plan.n_emit < 1 || plan.n_emit > PG_MAX_SORT_EMIT)
+            throw std::runtime_error("WINDOW: n_emit must be 1..16");
+        if (plan.n_funcs < 1 || plan.n_funcs > PG_MAX_WIN_FUNCS)
+            throw std::runtime_error("WINDOW: n_funcs must be 1..8");
+        n_keys = plan.n_keys;
+        key_col = plan.key_col;
+        order = plan.order;
+        n_emit = plan.n_emit;
+        emit_cols = plan.emit_cols;
+        init_keys_and_emit();
+        for (int i = 0; i < plan.n_funcs; i++) {
+            const pg_win_spec& f = plan.funcs[i];
+            if (f.func < PG_WIN_ROW_NUMBER || f.func > PG_WIN_LEAD)
+                throw std::runtime_error(fn(i, "func") +
+                                         " is not a pg_win_func");
+            if (is_agg(f.func) && (f.frame < PG_FRAME_RANGE_RUNNING ||
+                                   f.frame > PG_FRAME_PARTITION))
+                throw std::runtime_error(fn(i, "frame") +
+                                         " is not a pg_win_frame");
+            if (is_shift(f.func) && f.offset < 0)
+                throw std::runtime_error(fn(i, "offset") + " is negative");
+            const bool reads = is_shift(f.func) ||
+                               (is_agg(f.func) && (f.func != PG_WIN_COUNT ||
+                                                   f.col >= 0));
+            if (reads && f.col < 0)
+                throw std::runtime_error(fn(i, "col") + " is negative (" +
+                                         func_name(f.func) +
+                                         " needs a column)");
+            arg_slot[i] = reads ? slot_of(f.col) : -1;
+        }
+    }
+    void check_more(const pg_page* in) override
+    {
+        for (int i = 0; i < plan.n_funcs; i++) {
+            if (arg_slot[i] < 0) continue;
+            const pg_win_spec& f = plan.funcs[i];
+            const std::string name = fn(i, "col");
+            check_col(in, name, f.col, false);
+            const int tag = in->cols[f.col].tag;
+            if (f.func >= PG_WIN_SUM && f.func <= PG_WIN_MAX &&
+                (tag == PG_T_I128 || tag == PG_T_F64))
+                throw std::runtime_error(
+                    name + " = " + std::to_string(f.col) +
+                    ": I128 and F64 columns are unsupported under " +
+                    func_name(f.func));
+        }
+    }
+    void add_input(const pg_page* in) override
+    {
+        if (!failed.empty()) throw std::runtime_error(failed);
+        SortedInputOp::add_input(in);
+    }
+    /* the three launches of one aggregate's segmented scan */
+    template <int K>
+    void scan_agg(const win_arg& a, const uint32_t* ids, const uint8_t* flags,
+                  int64_t n, int64_t chunk, int nb, void* carry,
+                  uint64_t* s_lo, int64_t* s_hi, uint32_t* s_cnt)
+    {
+        auto* c = (win_acc<K>*)carry;
+        hipLaunchKernelGGL(k_win_agg_reduce<K>, dim3(nb), dim3(256), 0,
+                           g_stream, a, ids, flags, n, chunk, c);
+        hipLaunchKernelGGL(k_win_agg_carry<K>, dim3(1), dim3(256), 0,
+                           g_stream, c, nb);
+        hipLaunchKernelGGL(k_win_agg_scan<K>, dim3(nb), dim3(256), 0,
+                           g_stream, a, ids, flags, n, chunk,
+                           (const win_acc<K>*)c, s_lo, s_hi, s_cnt);
+    }
+    /* everything after the sort, for n >= 1: flags and bounds (three
+     * launches), then per function its scan (three launches, aggregates
+     * only) and its emit.  All on g_stream, one host read at the end. */
+    void run_functions(int64_t n, const uint32_t* ids, OutPage& op)
+    {
+        int64_t chunk;
+        const int nb = sort_geometry(n, &chunk);
+        const int grid = (int)std::min<int64_t>((n + 255) / 256, 2048);
+        DevBuf flags, fwdc, bwdc, bounds, errs, carry, s_lo, s_hi, s_cnt;
+        flags.alloc((size_t)n);
+        fwdc.alloc((size_t)nb * sizeof(win_fwd));
+        bwdc.alloc((size_t)nb * sizeof(win_bwd));
+        bounds.alloc((size_t)n * 4 * 5);
+        uint32_t* part_start = (uint32_t*)bounds.p;
+        uint32_t* peer_start = part_start + n;
+        uint32_t* heads = peer_start + n;
+        uint32_t* part_end = heads + n;
+        uint32_t* peer_end = part_end + n;
+        win_keys wk{};
+        wk.n_keys = plan.n_keys;
+        wk.n_part = plan.n_partition_keys;
+        for (int k = 0; k < plan.n_keys; k++) {
+            const Slot& s = slots[key_slot[k]];
+            wk.col[k] = s.all.p;
+            wk.mask[k] = s.has_mask ? (const uint8_t*)s.all_mask.p : nullptr;
+            wk.tag[k] = s.tag;
+        }
+        hipLaunchKernelGGL(k_win_flags, dim3(nb), dim3(256), 0, g_stream, wk,
+                           ids, n, chunk, (uint8_t*)flags.p,
+                           (win_fwd*)fwdc.p, (win_bwd*)bwdc.p);
+        hipLaunchKernelGGL(k_win_bounds_carry, dim3(1), dim3(256), 0,
+                           g_stream, (win_fwd*)fwdc.p, (win_bwd*)bwdc.p, nb);
+        hipLaunchKernelGGL(k_win_bounds, dim3(nb), dim3(256), 0, g_stream,
+                           (const uint8_t*)flags.p, n, chunk,
+                           (const win_fwd*)fwdc.p, (const win_bwd*)bwdc.p,
+                           part_start, peer_start, heads, part_end, peer_end);
+        bool any_agg = false, any_val = false, any_sum = false;
+        for (int i = 0; i < plan.n_funcs; i++) {
+            const int f = plan.funcs[i].func;
+            any_agg |= is_agg(f);
+            any_val |= f >= PG_WIN_SUM && f <= PG_WIN_MAX;
+            any_sum |= f == PG_WIN_SUM;
+        }
+        if (any_agg) {
+            carry.alloc((size_t)nb * sizeof(win_acc<PG_WIN_SUM>));
+            s_cnt.alloc((size_t)n * 4);
+        }
+        if (any_val) s_lo.alloc((size_t)n * 8);
+        if (any_sum) s_hi.alloc((size_t)n * 8);
+        errs.alloc(PG_MAX_WIN_FUNCS * 4);
+        errs.zero();
+        for (int i = 0; i < plan.n_funcs; i++) {
+            const pg_win_spec& f = plan.funcs[i];
+            const Slot* s = arg_slot[i] >= 0 ? &slots[arg_slot[i]] : nullptr;
+            const uint8_t* smask =
+                s && s->has_mask ? (const uint8_t*)s->all_mask.p : nullptr;
+            if (is_agg(f.func)) {
+                win_arg a{};
+                if (s) {
+                    a.col = s->all.p;
+                    a.mask = smask;
+                    a.tag = s->tag;
+                }
+                const uint8_t* fl = (const uint8_t*)flags.p;
+                uint64_t* lo = (uint64_t*)s_lo.p;
+                int64_t* hi = (int64_t*)s_hi.p;
+                uint32_t* cnt = (uint32_t*)s_cnt.p;
+                switch (f.func) {
+                    case PG_WIN_COUNT:
+                        scan_agg<PG_WIN_COUNT>(a, ids, fl, n, chunk, nb,
+                                               carry.p, lo, hi, cnt);
+                        break;
+                    case PG_WIN_SUM:
+                        scan_agg<PG_WIN_SUM>(a, ids, fl, n, chunk, nb,
+                                             carry.p, lo, hi, cnt);
+                        break;
+                    case PG_WIN_MIN:
+                        scan_agg<PG_WIN_MIN>(a, ids, fl, n, chunk, nb,
+                                             carry.p, lo, hi, cnt);
+                        break;
+                    default:
+                        scan_agg<PG_WIN_MAX>(a, ids, fl, n, chunk, nb,
+                                             carry.p, lo, hi, cnt);
+                        break;
+                }
+            }
+            const pg_col& out = op.pg.cols[plan.n_emit + i];
+            win_emit e{};
+            e.func = f.func;
+            e.frame = f.frame;
+            e.width = (int)type_size(out.tag);
+            e.offset = f.offset;
+            e.ids = ids;
+            e.part_start = part_start;
+            e.peer_start = peer_start;
+            e.heads = heads;
+            e.part_end = part_end;
+            e.peer_end = peer_end;
+            e.s_lo = (const uint64_t*)s_lo.p;
+            e.s_hi = (const int64_t*)s_hi.p;
+            e.s_cnt = (const uint32_t*)s_cnt.p;
+            if (is_shift(f.func)) {
+                e.col = s->all.p;
+                e.cmask = smask;
+            }
+            e.out = out.data;
+            e.omask = (uint8_t*)out.null_mask;
+            e.err = (int32_t*)errs.p + i;
+            hipLaunchKernelGGL(k_win_emit, dim3(grid), dim3(256), 0, g_stream,
+                               e, n);
+        }
+        int32_t herr[PG_MAX_WIN_FUNCS];
+        CHKV(hipMemcpyAsync(herr, errs.p, sizeof(herr), hipMemcpyDeviceToHost,
+                            g_stream));
+        CHKV(hipStreamSynchronize(g_stream));
+        for (int i = 0; i < plan.n_funcs && failed.empty(); i++)
+            if (herr[i])
+                failed = fname("funcs", i) +
+                         ": a SUM does not fit int64 (col " +
+                         std::to_string(plan.funcs[i].col) + ")";
+    }
+    void finish() override
+    {
+        if (!failed.empty()) throw std::runtime_error(failed);
+        const int64_t n = n_total;
+        for (auto& s : slots) concat(s);
+        DevBuf idA, idB;
+        const uint32_t* ids = sort_ids(n, idA, idB);
+        OutPage op;
+        op.pg.n_rows = n;
+        op.pg.n_cols = plan.n_emit + plan.n_funcs;
+        gather_emit(op, ids, n);
+        for (int i = 0; i < plan.n_funcs; i++) {
+            const int f = plan.funcs[i].func;
+            /* ranks, COUNT and SUM are I64; MIN, MAX, LAG and LEAD have
+             * their column's type.  SUM, MIN, MAX, LAG and LEAD can be
+             * null and always carry a mask. */
+            const bool typed_by_col = f >= PG_WIN_MIN;
+            const bool masked = f >= PG_WIN_SUM;
+            pg_col& c = op.pg.cols[plan.n_emit + i];
+            c.tag = typed_by_col ? slots[arg_slot[i]].tag : PG_T_I64;
+            c.on_device = 1;
+            op.dev.emplace_back();
+            op.dev.back().alloc((size_t)n * type_size(c.tag));
+            c.data = op.dev.back().p;
+            c.null_mask = nullptr;
+            if (masked) {
+                op.dev.emplace_back();
+                op.dev.back().alloc((size_t)n);
+                c.null_mask = (const uint8_t*)op.dev.back().p;
+            }
+        }
+        if (n > 0) run_functions(n, ids, op);
+        CHKV(hipStreamSynchronize(g_stream));
+        free_slots();
+        if (!failed.empty()) throw std::runtime_error(failed);
         outq.push_back(std::move(op));
     }
 };
@@ -6299,6 +7094,15 @@ extern "C" pg_status pg_op_create(int32_t kind, const void* plan,
                 if (plan_bytes != sizeof(pg_plan_order_by))
                     return seterr("bad plan size");
                 auto* o = new OrderByOp();
+                op.reset(o);
+                memcpy(&o->plan, plan, sizeof(o->plan));
+                o->init();
+                break;
+            }
+            case PG_OP_WINDOW: {
+                if (plan_bytes != sizeof(pg_plan_window))
+                    return seterr("bad plan size");
+                auto* o = new WindowOp();
                 op.reset(o);
                 memcpy(&o->plan, plan, sizeof(o->plan));
                 o->init();
@@ -6927,6 +7731,7 @@ extern "C" int32_t pg_abi_plan_size(int32_t kind)
         case PG_OP_PARTITION: return (int32_t)sizeof(pg_plan_partition);
         case PG_OP_GROUPBY_MULTI: return (int32_t)sizeof(pg_plan_groupby);
         case PG_OP_ORDER_BY: return (int32_t)sizeof(pg_plan_order_by);
+        case PG_OP_WINDOW: return (int32_t)sizeof(pg_plan_window);
         default: return -1;
     }
 }

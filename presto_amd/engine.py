@@ -26,9 +26,14 @@ JOIN_INNER, JOIN_PROBE_OUTER, JOIN_LOOKUP_OUTER, JOIN_FULL_OUTER = 0, 4, 5, 6
  AGG_MIN, AGG_MAX) = range(6)
 (OP_FILTER_PROJECT, OP_HASH_AGG_SMALL, OP_HASH_BUILD, OP_LOOKUP_JOIN,
  OP_TOPN, OP_PARTITION, OP_GROUPBY_MULTI, OP_ORDER_BY) = range(1, 9)
+OP_WINDOW = 10  # 9 is left unassigned
 # pg_sort_order (SortOrder.java)
 (SORT_ASC_NULLS_FIRST, SORT_ASC_NULLS_LAST, SORT_DESC_NULLS_FIRST,
  SORT_DESC_NULLS_LAST) = range(4)
+# pg_win_func, pg_win_frame
+(WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_COUNT, WIN_SUM, WIN_MIN,
+ WIN_MAX, WIN_LAG, WIN_LEAD) = range(9)
+FRAME_RANGE_RUNNING, FRAME_ROWS_RUNNING, FRAME_PARTITION = range(3)
 
 _NP_TAG = {np.dtype(np.uint8): T_U8, np.dtype(np.int32): T_I32,
            np.dtype(np.int64): T_I64, np.dtype(np.float64): T_F64}
@@ -129,6 +134,19 @@ class PlanOrderBy(C.Structure):
     _fields_ = [("n_keys", C.c_int32), ("key_col", C.c_int32 * 4),
                 ("order", C.c_int32 * 4), ("n_emit", C.c_int32),
                 ("emit_cols", C.c_int32 * 16), ("limit", C.c_int64)]
+
+
+class WinSpec(C.Structure):
+    _fields_ = [("func", C.c_int32), ("col", C.c_int32),
+                ("frame", C.c_int32), ("pad", C.c_int32),
+                ("offset", C.c_int64)]
+
+
+class PlanWindow(C.Structure):
+    _fields_ = [("n_keys", C.c_int32), ("n_partition_keys", C.c_int32),
+                ("key_col", C.c_int32 * 4), ("order", C.c_int32 * 4),
+                ("n_emit", C.c_int32), ("emit_cols", C.c_int32 * 16),
+                ("n_funcs", C.c_int32), ("funcs", WinSpec * 8)]
 
 
 class _Lib:

@@ -13,6 +13,10 @@ import ctypes as C
 from .engine import (
     Pred, Proj, Agg, PlanFilterProject, PlanHashAggSmall, PlanHashBuild,
     PlanLookupJoin, PlanGroupBy, PlanTopN, PlanPartition, PlanOrderBy,
+    PlanWindow, WinSpec,
+    WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_COUNT, WIN_SUM, WIN_MIN,
+    WIN_MAX, WIN_LAG, WIN_LEAD,
+    FRAME_RANGE_RUNNING, FRAME_ROWS_RUNNING, FRAME_PARTITION,
     SORT_ASC_NULLS_FIRST, SORT_ASC_NULLS_LAST, SORT_DESC_NULLS_FIRST,
     SORT_DESC_NULLS_LAST,
     CMP_CONTAINS2, CMP_NOT_CONTAINS2, CMP_IS_NULL, CMP_IS_NOT_NULL,
@@ -289,6 +293,66 @@ def order_by(keys, emit, limit=0):
     if p.n_emit == 0:
         raise ValueError("emit_cols: ORDER BY needs at least one column")
     p.limit = limit
+    return p
+
+
+# ---- window functions (pg_win_spec) ----
+def row_number():
+    return WinSpec(WIN_ROW_NUMBER, -1, 0, 0, 0)
+
+
+def rank():
+    return WinSpec(WIN_RANK, -1, 0, 0, 0)
+
+
+def dense_rank():
+    return WinSpec(WIN_DENSE_RANK, -1, 0, 0, 0)
+
+
+def win_count(col=None, frame=FRAME_RANGE_RUNNING):
+    """count(*) over the frame, or count(col): its non-null rows."""
+    return WinSpec(WIN_COUNT, -1 if col is None else col, frame, 0, 0)
+
+
+def win_sum(col, frame=FRAME_RANGE_RUNNING):
+    return WinSpec(WIN_SUM, col, frame, 0, 0)
+
+
+def win_min(col, frame=FRAME_RANGE_RUNNING):
+    return WinSpec(WIN_MIN, col, frame, 0, 0)
+
+
+def win_max(col, frame=FRAME_RANGE_RUNNING):
+    return WinSpec(WIN_MAX, col, frame, 0, 0)
+
+
+def lag(col, offset=1):
+    """col of the row `offset` rows back in its partition, else null."""
+    return WinSpec(WIN_LAG, col, 0, 0, offset)
+
+
+def lead(col, offset=1):
+    return WinSpec(WIN_LEAD, col, 0, 0, offset)
+
+
+def window(partition_by, order_by, emit, funcs):
+    """Window functions over PARTITION BY partition_by ORDER BY order_by:
+    both are sequences of (col, order) pairs (see asc / desc), either may
+    be empty; emit lists the input channels to pass through, funcs the
+    WinSpec entries (row_number(), win_sum(...), lag(...) ...) whose
+    columns follow them in the output."""
+    partition_by, order_by = list(partition_by), list(order_by)
+    keys = partition_by + order_by
+    p = PlanWindow()
+    p.n_keys = _fill(p.key_col, "key_col", [c for c, _ in keys])
+    _fill(p.order, "order", [o for _, o in keys])
+    p.n_partition_keys = len(partition_by)
+    p.n_emit = _fill(p.emit_cols, "emit_cols", emit)
+    p.n_funcs = _fill(p.funcs, "funcs", funcs)
+    if p.n_emit == 0:
+        raise ValueError("emit_cols: WINDOW needs at least one column")
+    if p.n_funcs == 0:
+        raise ValueError("funcs: WINDOW needs at least one function")
     return p
 
 
