@@ -66,6 +66,11 @@ void pg_hot_reset(void);
  * Q1-shape kernel rather than the generic one (tests pin which plans
  * take it) */
 int64_t pg_q1_fast_launches(void);
+/* how many agg_table build pages this process has sent to the staged
+ * multi-row insert kernel rather than the generic direct insert (the
+ * packed Q3/Q5 orders-build shape; PG_BUILD_STAGED=0 in the environment
+ * at build creation forces the generic kernel) */
+int64_t pg_build_staged_launches(void);
 
 /* ---- Page / Block descriptors (SURVEY.md §8b struct) ----
  * Concrete layouts follow the Java blocks: fixed-width values array +

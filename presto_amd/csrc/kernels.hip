@@ -161,6 +161,11 @@ extern "C" double pg_hot_max_ms(void) { return g_hot_max_ms; }
 extern "C" void pg_hot_reset(void) { g_hot_max_ms = 0.0; }
 static int64_t g_q1_fast_launches = 0;
 extern "C" int64_t pg_q1_fast_launches(void) { return g_q1_fast_launches; }
+static int64_t g_build_staged_launches = 0;
+extern "C" int64_t pg_build_staged_launches(void)
+{
+    return g_build_staged_launches;
+}
 
 /* ------------------------------------------------------------------ */
 /* device helpers                                                     */
@@ -1437,6 +1442,224 @@ __global__ __launch_bounds__(256) void k_tbl_insert_direct(
     }
     /* one atomic per wave, not per insert (a single-address atomicAdd per
      * row serializes the whole grid) */
+    my_inserted = d_bfly_i64(my_inserted);
+    my_overflow = d_bfly_i64(my_overflow);
+    my_packerr = d_bfly_i64(my_packerr);
+    if ((threadIdx.x & 63) == 0) {
+        if (my_inserted) atomicAdd(inserted, (unsigned long long)my_inserted);
+        if (my_overflow) atomicAdd(overflow, (unsigned long long)my_overflow);
+        if (my_packerr) atomicAdd(pack_err, (unsigned long long)my_packerr);
+    }
+}
+
+/* Staged direct insert: the Q3/Q5 orders-build shape of
+ * k_tbl_insert_direct (packed slot word, 0-2 literal int32 predicates,
+ * optional dense flag semijoin, optional dense u8 payload lookup; BuildOp
+ * gates it per page).  The generic kernel walks one row per thread
+ * through a chain of dependent misses (predicate column -> semijoin key
+ * -> flag gather -> build key -> CAS); here a thread owns BS_R
+ * consecutive rows of a 1024-row block tile and every load of a stage is
+ * issued for all of them before any result is consumed:
+ *   A  nontemporal vector loads of the predicate / semijoin / lookup /
+ *      build-key columns, unconditionally;
+ *   B  predicates, then the dense flag and lookup gathers of the rows
+ *      that pass, issued together;
+ *   C  pack and bitmap range checks, bitmap set, bounded CAS probe, tag
+ *      store — per row exactly what the generic kernel does; the first
+ *      CAS of every surviving row goes out before any result is read.
+ * Measured on the SF100 Q3 build (profiles/build_staged.json): 2.80 ms ->
+ * 2.04 ms.  Deferring the build-key load to the ~10% of rows that pass
+ * (2.08 ms) and compacting a tile's survivors through LDS so that the CAS
+ * chains run in full waves (2.13 ms) both measured slower and are not
+ * kept.  No block waits on another; every loop is bounded. */
+#define BS_R 4
+#define BS_TILE (256 * BS_R)
+struct staged_args {
+    const int32_t* pc[2]; /* predicate columns (I32) */
+    int64_t pval[2];
+    int32_t pop[2];
+    int32_t n_preds;
+    const int64_t* sk;    /* semijoin key column, or null */
+    const uint8_t* flags; /* dense flag set over keys 1..nflags */
+    int64_t nflags;
+    const int64_t* lk;    /* payload lookup key column, or null */
+    const uint8_t* lu;    /* dense u8 lookup over keys 1..lucap */
+    int64_t lucap;
+    const int64_t* key;   /* build key column */
+    const void* pay;      /* payload column (no lookup, pay_pred < 0) */
+    int32_t pay_tag;
+    int32_t pay_pred;     /* >= 0: the payload is predicate column #n */
+    int64_t n;
+};
+__device__ inline bool d_cmp_i64(int32_t op, int64_t v, int64_t x)
+{
+    switch (op) {
+        case PG_CMP_LT: return v < x;
+        case PG_CMP_LE: return v <= x;
+        case PG_CMP_GT: return v > x;
+        case PG_CMP_GE: return v >= x;
+        case PG_CMP_EQ: return v == x;
+        default: return v != x;
+    }
+}
+__device__ inline void d_bs_load_i32(const int32_t* p, int64_t base,
+                                     int64_t n, bool full, int64_t* out)
+{
+    typedef int vi4 __attribute__((ext_vector_type(4)));
+    if (full) {
+        vi4 v = __builtin_nontemporal_load((const vi4*)(p + base));
+#pragma unroll
+        for (int j = 0; j < BS_R; j++) out[j] = v[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < BS_R; j++)
+            out[j] = base + j < n ? p[base + j] : 0;
+    }
+}
+__device__ inline void d_bs_load_i64(const int64_t* p, int64_t base,
+                                     int64_t n, bool full, int64_t* out)
+{
+    typedef long vl2 __attribute__((ext_vector_type(2)));
+    if (full) {
+#pragma unroll
+        for (int j = 0; j < BS_R; j += 2) {
+            vl2 v = __builtin_nontemporal_load((const vl2*)(p + base + j));
+            out[j] = v[0];
+            out[j + 1] = v[1];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < BS_R; j++)
+            out[j] = base + j < n ? p[base + j] : 0;
+    }
+}
+/* the probe loop of k_tbl_insert_direct for a packed word, entered with
+ * the result of the first CAS already in hand */
+__device__ inline void d_bs_probe(int64_t* keys, uint8_t* tags,
+                                  int64_t mask, uint64_t h, int64_t s,
+                                  int64_t word, int64_t old,
+                                  int64_t& my_inserted, int64_t& my_overflow)
+{
+    int64_t tries = 0;
+    for (;;) {
+        if (old == TBL_EMPTY || old == word) {
+            if (old == TBL_EMPTY) {
+                my_inserted++;
+                if (tags) tags[s] = d_tbl_tag(h);
+            }
+            return;
+        }
+        if (++tries > mask) { /* table full: bounded give-up */
+            my_overflow++;
+            return;
+        }
+        s = (s + 1) & mask;
+        old = atomicCAS((unsigned long long*)&keys[s],
+                        (unsigned long long)TBL_EMPTY,
+                        (unsigned long long)word);
+    }
+}
+__global__ __launch_bounds__(256) void k_tbl_insert_staged(
+    staged_args a, int32_t pbits, int64_t* keys, uint8_t* tags,
+    int64_t mask, unsigned long long* inserted,
+    unsigned long long* overflow, unsigned long long* pack_err,
+    unsigned long long* kbits, int64_t bmax, unsigned long long* bm_err)
+{
+    const int64_t n = a.n;
+    const int64_t n_tiles = (n + BS_TILE - 1) / BS_TILE;
+    int64_t my_inserted = 0, my_overflow = 0, my_packerr = 0;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t base = tile * BS_TILE + (int64_t)threadIdx.x * BS_R;
+        const bool full = base + BS_R <= n; /* else: scalar tail */
+        /* ---- stage A ---- */
+        int64_t pv[2][BS_R] = {}, skv[BS_R] = {}, lkv[BS_R] = {}, kv[BS_R];
+        if (a.n_preds > 0) d_bs_load_i32(a.pc[0], base, n, full, pv[0]);
+        if (a.n_preds > 1) d_bs_load_i32(a.pc[1], base, n, full, pv[1]);
+        if (a.sk) d_bs_load_i64(a.sk, base, n, full, skv);
+        if (a.lk) d_bs_load_i64(a.lk, base, n, full, lkv);
+        d_bs_load_i64(a.key, base, n, full, kv);
+        /* ---- stage B ---- */
+        bool ok[BS_R];
+#pragma unroll
+        for (int j = 0; j < BS_R; j++) {
+            ok[j] = base + j < n;
+            if (a.n_preds > 0)
+                ok[j] = ok[j] && d_cmp_i64(a.pop[0], pv[0][j], a.pval[0]);
+            if (a.n_preds > 1)
+                ok[j] = ok[j] && d_cmp_i64(a.pop[1], pv[1][j], a.pval[1]);
+            /* keys outside the dense ranges are dropped before the gather */
+            if (a.lk) ok[j] = ok[j] && lkv[j] >= 1 && lkv[j] <= a.lucap;
+            if (a.sk) ok[j] = ok[j] && skv[j] >= 1 && skv[j] <= a.nflags;
+        }
+        uint8_t fl[BS_R], plv[BS_R];
+        int64_t pay[BS_R];
+#pragma unroll
+        for (int j = 0; j < BS_R; j++) {
+            fl[j] = 1;
+            plv[j] = 0;
+            pay[j] = 0;
+            if (!ok[j]) continue;
+            if (a.sk) fl[j] = a.flags[skv[j] - 1];
+            if (a.lk) plv[j] = a.lu[lkv[j] - 1];
+            else if (a.pay_pred < 0) {
+                if (a.pay_tag == PG_T_I32)
+                    pay[j] = ((const int32_t*)a.pay)[base + j];
+                else if (a.pay_tag == PG_T_U8)
+                    pay[j] = ((const uint8_t*)a.pay)[base + j];
+                else
+                    pay[j] = ((const int64_t*)a.pay)[base + j];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < BS_R; j++) {
+            ok[j] = ok[j] && fl[j] != 0;
+            if (a.lk) pay[j] = plv[j];
+            else if (a.pay_pred >= 0)
+                pay[j] = a.pay_pred ? pv[1][j] : pv[0][j];
+        }
+        /* ---- stage C ---- */
+        int64_t word[BS_R];
+#pragma unroll
+        for (int j = 0; j < BS_R; j++) {
+            word[j] = 0;
+            if (!ok[j]) continue;
+            const int64_t key = kv[j];
+            if (key < 0 || key >= (1ll << (63 - pbits)) || pay[j] < 0 ||
+                pay[j] >= (1ll << pbits)) {
+                my_packerr++;
+                ok[j] = false;
+                continue;
+            }
+            if (kbits) {
+                if ((uint64_t)(key - 1) >= (uint64_t)bmax) {
+                    atomicAdd(bm_err, 1ull);
+                    ok[j] = false;
+                    continue;
+                }
+                d_kbit_set(kbits, key);
+            }
+            word[j] = (key << pbits) | pay[j];
+        }
+        uint64_t h[BS_R];
+        int64_t old[BS_R];
+#pragma unroll
+        for (int j = 0; j < BS_R; j++) {
+            h[j] = pg_murmur3_finalize(pg_bigint_hash(kv[j]));
+            old[j] = 0;
+            if (ok[j])
+                old[j] = atomicCAS(
+                    (unsigned long long*)&keys[h[j] & (uint64_t)mask],
+                    (unsigned long long)TBL_EMPTY,
+                    (unsigned long long)word[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < BS_R; j++)
+            if (ok[j])
+                d_bs_probe(keys, tags, mask, h[j],
+                           (int64_t)(h[j] & (uint64_t)mask), word[j], old[j],
+                           my_inserted, my_overflow);
+    }
+    /* one atomic per wave, as in k_tbl_insert_direct */
     my_inserted = d_bfly_i64(my_inserted);
     my_overflow = d_bfly_i64(my_overflow);
     my_packerr = d_bfly_i64(my_packerr);
@@ -4845,6 +5068,66 @@ struct BuildOp : Op {
     bool part = false;
     int32_t P = 1, Kact = 1, capp_bits = 0;
     DevBuf stage, cursorb, barb;
+    bool staged = true; /* direct builds may use k_tbl_insert_staged */
+    /* does this page of a direct agg_table build fit the staged insert
+     * kernel?  Fills its arguments when it does; everything else stays on
+     * k_tbl_insert_direct. */
+    bool staged_fit(const pg_page& pg, const Table* semi, const Table* lu,
+                    staged_args* sa) const
+    {
+        auto vec_i64 = [](const pg_col& c) {
+            return c.tag == PG_T_I64 && !c.null_mask &&
+                   ((uintptr_t)c.data & 15) == 0;
+        };
+        if (!staged || plan.pack_bits <= 0 || plan.n_payload != 1)
+            return false;
+        if (plan.n_preds < 0 || plan.n_preds > 2) return false;
+        staged_args a{};
+        a.n = pg.n_rows;
+        a.n_preds = plan.n_preds;
+        for (int p = 0; p < plan.n_preds; p++) {
+            const pg_pred& pr = plan.preds[p];
+            const pg_col& c = pg.cols[pr.col];
+            if (pr.rhs_col != 0 || pr.op < PG_CMP_LT || pr.op > PG_CMP_NE ||
+                c.tag != PG_T_I32 || c.null_mask ||
+                ((uintptr_t)c.data & 15) != 0)
+                return false;
+            a.pc[p] = (const int32_t*)c.data;
+            a.pval[p] = pr.ival;
+            a.pop[p] = pr.op;
+        }
+        const pg_col& kc = pg.cols[plan.key_col];
+        if (!vec_i64(kc)) return false;
+        a.key = (const int64_t*)kc.data;
+        if (semi) {
+            const pg_col& sc = pg.cols[plan.semijoin_col];
+            if (!semi->dense || semi->ptag.empty() ||
+                semi->ptag[0] != PG_T_U8 || !vec_i64(sc))
+                return false;
+            a.sk = (const int64_t*)sc.data;
+            a.flags = (const uint8_t*)semi->payload[0].p;
+            a.nflags = semi->cap;
+        }
+        a.pay_pred = -1;
+        if (lu) {
+            const pg_col& lc = pg.cols[plan.payload_lookup_key_col];
+            if (!lu->dense || !vec_i64(lc)) return false; /* u8: checked */
+            a.lk = (const int64_t*)lc.data;
+            a.lu = (const uint8_t*)lu->payload[0].p;
+            a.lucap = lu->cap;
+        } else {
+            const pg_col& pc = pg.cols[plan.payload_col[0]];
+            if (pc.tag != PG_T_I32 && pc.tag != PG_T_U8 &&
+                pc.tag != PG_T_I64)
+                return false;
+            a.pay = pc.data;
+            a.pay_tag = pc.tag;
+            for (int p = 0; p < plan.n_preds; p++)
+                if (plan.preds[p].col == plan.payload_col[0]) a.pay_pred = p;
+        }
+        *sa = a;
+        return true;
+    }
     void init()
     {
         t.reset(new Table());
@@ -4917,13 +5200,18 @@ struct BuildOp : Op {
              * the 256 MiB L3 (see k_part_scatter/insert) */
             /* A/B-measured up to 150M inserts / 2 GB tables: the direct
              * random insert WINS OR TIES at every size this hardware can
-             * hold (it is atomic-op-rate bound, not locality bound), so
+             * hold (not a locality effect: the generic kernel was bound
+             * by its per-row evaluation chain), so
              * the radix path engages only beyond measured scales; it
              * stays parity-tested and selectable via PG_PART_MIN_SLOTS */
             int64_t part_min = 512ll << 20;
             if (const char* ep = getenv("PG_PART_MIN_SLOTS"))
                 if (atoll(ep) > 0) part_min = atoll(ep);
             part = cap >= part_min;
+            /* PG_BUILD_STAGED=0 keeps every page on k_tbl_insert_direct */
+            staged = true;
+            if (const char* es = getenv("PG_BUILD_STAGED"))
+                staged = atoi(es) != 0;
             /* byte tags reject probe misses from a cap-sized L3-resident
              * array (8x denser than the key lines).  For partitioned
              * builds the tag store lands in the L3-resident region wave
@@ -5142,6 +5430,26 @@ struct BuildOp : Op {
                     1 + plan.n_payload,
                     (unsigned long long*)counters.p + 2);
                 hot_end();
+                CHKV(hipStreamSynchronize(g_stream));
+                return;
+            }
+            staged_args sa;
+            if (staged_fit(sp.pg, semi, lu, &sa)) {
+                int64_t tiles = (sa.n + BS_TILE - 1) / BS_TILE;
+                int grid = (int)(tiles < 4096 ? (tiles > 0 ? tiles : 1)
+                                              : 4096);
+                hot_begin();
+                hipLaunchKernelGGL(
+                    k_tbl_insert_staged, dim3(grid), dim3(256), 0, g_stream,
+                    sa, plan.pack_bits, (int64_t*)t->keys.p,
+                    (uint8_t*)t->tags.p, t->mask,
+                    (unsigned long long*)counters.p,
+                    (unsigned long long*)counters.p + 1,
+                    (unsigned long long*)counters.p + 3,
+                    (unsigned long long*)t->kbits.p, t->bmax,
+                    (unsigned long long*)counters.p + 4);
+                hot_end();
+                g_build_staged_launches++;
                 CHKV(hipStreamSynchronize(g_stream));
                 return;
             }
