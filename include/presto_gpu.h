@@ -71,6 +71,12 @@ int64_t pg_q1_fast_launches(void);
  * packed Q3/Q5 orders-build shape; PG_BUILD_STAGED=0 in the environment
  * at build creation forces the generic kernel) */
 int64_t pg_build_staged_launches(void);
+/* how many grouped (mode 1, single aggregate) LOOKUP_JOIN finishes this
+ * process has extracted from the table's hit list (a gather of the slots
+ * the probes first touched) rather than by scanning the accumulator array
+ * (PG_GROUPS_LIST=0 in the environment at build creation forces the
+ * scan) */
+int64_t pg_groups_list_extractions(void);
 
 /* ---- Page / Block descriptors (SURVEY.md §8b struct) ----
  * Concrete layouts follow the Java blocks: fixed-width values array +

@@ -166,6 +166,11 @@ extern "C" int64_t pg_build_staged_launches(void)
 {
     return g_build_staged_launches;
 }
+static int64_t g_groups_list_extractions = 0;
+extern "C" int64_t pg_groups_list_extractions(void)
+{
+    return g_groups_list_extractions;
+}
 
 /* ------------------------------------------------------------------ */
 /* device helpers                                                     */
@@ -2038,16 +2043,76 @@ __device__ inline void d_atomic_add_dec_ck(unsigned long long* slot,
     if (((old ^ nv) & (ticks ^ nv)) < 0 && ovf) atomicAdd(ovf, 1ull);
 }
 
+/* Hit list of a table (Table::hits): the mode-1 probes append every slot
+ * whose count they take from 0, so extraction gathers those slots.  The
+ * add that returns 0 is unique per slot and accumulator lifetime, so each
+ * group is appended exactly once.  First touches are rare (0.2 % of Q3's
+ * probe rows) and the cursor is one address, so a wave stages them in 64
+ * LDS entries of its own and flushes a full buffer with one cursor add
+ * and one coalesced store.  The staging is wave-synchronous: every lane
+ * of the wave calls in, so the probe loops bound their trip count by the
+ * wave's first lane and predicate per lane. */
+struct hit_list {
+    void* ents; /* null: do not append */
+    unsigned long long* cursor;
+    int64_t cap; /* entries; a flush never stores beyond it */
+    int32_t wide; /* int64 entries (cap > 2^32), else uint32 */
+};
+
+__device__ inline void d_hits_flush(const hit_list& hl,
+                                    volatile int64_t* wbuf, int cnt)
+{
+    const int lane = threadIdx.x & 63;
+    int64_t g = 0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0)
+        g = (int64_t)atomicAdd(hl.cursor, (unsigned long long)cnt);
+    g = __shfl(g, 0, WAVE);
+    if (lane < cnt && g + lane < hl.cap) {
+        int64_t s = wbuf[lane];
+        if (hl.wide)
+            ((int64_t*)hl.ents)[g + lane] = s;
+        else
+            ((uint32_t*)hl.ents)[g + lane] = (uint32_t)s;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+/* all 64 lanes call; lanes with ft stage their slot.  *cnt is the wave's
+ * staged count, the same in every lane. */
+__device__ inline void d_hits_stage(const hit_list& hl,
+                                    volatile int64_t* wbuf, int* cnt,
+                                    bool ft, int64_t slot)
+{
+    uint64_t m = d_ballot(ft);
+    if (!m) return;
+    const int lane = threadIdx.x & 63;
+    int pos = *cnt + __popcll(m & ((1ull << lane) - 1));
+    int total = *cnt + __popcll(m);
+    if (ft && pos < WAVE) wbuf[pos] = slot;
+    if (total >= WAVE) {
+        d_hits_flush(hl, wbuf, WAVE);
+        if (ft && pos >= WAVE) wbuf[pos - WAVE] = slot;
+        total -= WAVE;
+    }
+    *cnt = total;
+}
+
 /* probe + fused grouped SUM into table accumulators (Q3's
  * LookupJoinOperator + HashAggregationOperator fused; revenue summed
  * exactly in decimal ticks AND in 64.64 fixed point — order-independent,
  * so atomics preserve bit-determinism) */
-__global__ __launch_bounds__(256) void k_probe_agg(
+/* waves_per_eu(7): the occupancy this kernel had before the hit list */
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(7))) void k_probe_agg(
     pg_page pg, pg_plan_lookup_join plan, const int64_t* keys,
     const uint8_t* tags, int64_t mask, int64_t lmask, int32_t pbits,
     const unsigned long long* kbits, int64_t bmax,
     unsigned long long* acc, int32_t aw,
-    unsigned long long* ovf /* [tick overflow, SUM_F64 domain] */)
+    unsigned long long* ovf /* [tick overflow, SUM_F64 domain] */,
+    hit_list hl)
 {
     /* 4 CONSECUTIVE rows per thread with run dedup: neighboring rows
      * often share the join key (lineitem is clustered by orderkey), so
@@ -2059,9 +2124,19 @@ __global__ __launch_bounds__(256) void k_probe_agg(
     int64_t base =
         ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * C;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x * C;
-    for (; base < pg.n_rows; base += stride) {
+    const int lane = threadIdx.x & 63;
+    __shared__ int64_t hbuf[4][WAVE];
+    volatile int64_t* wbuf = hbuf[threadIdx.x >> 6];
+    int hcnt = 0;
+    /* the wave's first lane bounds the loop (lanes past the end run an
+     * empty row loop), so the hit-list staging sees whole waves */
+    for (; base - C * lane < pg.n_rows; base += stride) {
         const int64_t lim = base + C < pg.n_rows ? base + C : pg.n_rows;
         int64_t cur_key = 0, cur_slot = -2; /* -2 = no open run */
+        /* slots this thread first-touched in this pass: at most one per
+         * row, kept newest-first in registers */
+        int64_t fts[C] = {0, 0, 0, 0};
+        int nft = 0;
         int64_t run_dec = 0;
         long long run_min = INT64_MAX;
         uint64_t run_flo = 0, run_fhi = 0;
@@ -2079,7 +2154,14 @@ __global__ __launch_bounds__(256) void k_probe_agg(
                 atomicAdd(&s[2],
                           run_fhi + (old > ~run_flo ? 1ull : 0ull));
             }
-            atomicAdd(&s[aw - 1], (unsigned long long)run_cnt);
+            unsigned long long old =
+                atomicAdd(&s[aw - 1], (unsigned long long)run_cnt);
+            if (old == 0 && hl.ents) {
+#pragma unroll
+                for (int k = C - 1; k > 0; k--) fts[k] = fts[k - 1];
+                fts[0] = cur_slot;
+                nft++;
+            }
         };
         for (int64_t i = base; i < lim; i++) {
             if (!d_eval_preds(pg, plan.preds, plan.n_preds, i)) continue;
@@ -2122,7 +2204,13 @@ __global__ __launch_bounds__(256) void k_probe_agg(
             run_cnt++;
         }
         flush();
+        if (hl.ents) {
+#pragma unroll
+            for (int k = 0; k < C; k++)
+                d_hits_stage(hl, wbuf, &hcnt, k < nft, fts[k]);
+        }
     }
+    if (hl.ents && hcnt) d_hits_flush(hl, wbuf, hcnt);
 }
 
 /* specialized fused probe+agg for the Q3 shape (the codegen-analog
@@ -2135,13 +2223,18 @@ __global__ __launch_bounds__(256) void k_probe_agg(
  * parallelism is the lever.  ep/dc are loaded only for probe hits (~9%
  * of rows at SF100): skipping the 16 B money loads on the miss path
  * saves ~5 GB of the 600M-row pass. */
-__global__ __launch_bounds__(256) void k_probe_agg_q3(
+/* waves_per_eu(8): 4096 blocks are exactly two rounds at 8 waves per SIMD.
+ * The hit-list staging raised scalar-register use past that occupancy;
+ * the attribute has the compiler park the cold ones in vector lanes. */
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(8))) void k_probe_agg_q3(
     const int32_t* sd /* nullable pred col */, int32_t pred_op,
     int32_t pred_val, const int64_t* okey, const double* ep,
     const double* dc, int64_t n, const int64_t* keys, const uint8_t* tags,
     int64_t mask, int64_t lmask, int32_t pbits,
     const unsigned long long* kbits, int64_t bmax, int32_t dec_only,
-    unsigned long long* acc, int32_t aw, unsigned long long* ovf)
+    unsigned long long* acc, int32_t aw, unsigned long long* ovf,
+    hit_list hl)
 {
     typedef int vi2 __attribute__((ext_vector_type(2)));
     typedef long vl2 __attribute__((ext_vector_type(2)));
@@ -2151,7 +2244,27 @@ __global__ __launch_bounds__(256) void k_probe_agg_q3(
                         memory-level parallelism buys) */
     int64_t base0 = Q * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
     int64_t stride = Q * (int64_t)gridDim.x * blockDim.x;
-    for (int64_t base = base0; base < n; base += stride) {
+    const int lane = threadIdx.x & 63;
+    __shared__ int64_t hbuf[4][WAVE];
+    volatile int64_t* wbuf = hbuf[threadIdx.x >> 6];
+    int hcnt = 0;
+    /* the count adds of the previous pass: slot (< 0: no hit) and the
+     * count they found.  They are looked at one pass late, behind the
+     * next pass's probe loads, so the probe never waits on an add's
+     * return. */
+    int64_t pslot[Q];
+    unsigned long long pold[Q];
+#pragma unroll
+    for (int j = 0; j < Q; j++) {
+        pslot[j] = -1;
+        pold[j] = 1;
+    }
+    /* the wave's first lane bounds the loop (lanes past the end take the
+     * tail path with nothing selected), so the hit-list staging sees
+     * whole waves; one more pass than there are rows for drains the last
+     * pass's adds through the same staging code */
+    for (int64_t base = base0; base - Q * lane < n + stride;
+         base += stride) {
         int64_t k[Q];
         int32_t s[Q];
         bool sel[Q];
@@ -2205,9 +2318,16 @@ __global__ __launch_bounds__(256) void k_probe_agg_q3(
                 p = d_probe_next(p, lmask);
             }
         }
+        if (hl.ents) {
+#pragma unroll
+            for (int j = 0; j < Q; j++)
+                d_hits_stage(hl, wbuf, &hcnt,
+                             pslot[j] >= 0 && pold[j] == 0, pslot[j]);
+        }
 #pragma unroll
         for (int j = 0; j < Q; j++) {
             int64_t sl = slot[j];
+            pslot[j] = sl;
             if (sl < 0) continue;
             double e = ep[base + j], d = dc[base + j];
             int64_t cents = d_round_ticks(e * 100.0);
@@ -2228,9 +2348,11 @@ __global__ __launch_bounds__(256) void k_probe_agg_q3(
                 unsigned long long old = atomicAdd(&s[1], plo);
                 atomicAdd(&s[2], phi + (old > ~plo ? 1ull : 0ull));
             }
-            atomicAdd(&s[aw - 1], 1ull);
+            /* exactly one add per slot and accumulator lifetime finds 0 */
+            pold[j] = atomicAdd(&s[aw - 1], 1ull);
         }
     }
+    if (hl.ents && hcnt) d_hits_flush(hl, wbuf, hcnt);
 }
 
 /* mode 3: probe + grouped SUM keyed by the matched build row's first
@@ -3198,6 +3320,52 @@ __global__ __launch_bounds__(256) void k_groups_count(
         block_counts[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
 }
 
+/* one group row: key, payloads and accumulator words of slot i written to
+ * output row pos (shared by the scan and the hit-list extraction) */
+__device__ inline void d_group_row(
+    const int64_t* keys, const int32_t* head,
+    const unsigned long long* acc, int32_t aw, const build_payloads& bp,
+    int64_t i, int64_t pos, int64_t* out_key, const emit_outs& payload_outs,
+    int64_t* out_dec, double* out_f64, int64_t* out_cnt)
+{
+    /* range-group tables store no keys: the slot index IS key-1 */
+    int64_t kw = keys ? keys[i] : i + 1;
+    out_key[pos] = bp.pack_bits ? (kw >> bp.pack_bits) : kw;
+    int64_t r = bp.by_slot ? i : (int64_t)head[i];
+    for (int o = 0; o < bp.n; o++) {
+        int64_t pv = bp.pack_bits && o == 0
+                         ? (kw & ((1ll << bp.pack_bits) - 1))
+                         : 0;
+        switch (bp.tag[o]) {
+            case PG_T_U8:
+                ((uint8_t*)payload_outs.ptr[o])[pos] =
+                    bp.pack_bits && o == 0
+                        ? (uint8_t)pv
+                        : ((const uint8_t*)bp.ptr[o])[r];
+                break;
+            case PG_T_I32:
+                ((int32_t*)payload_outs.ptr[o])[pos] =
+                    bp.pack_bits && o == 0
+                        ? (int32_t)pv
+                        : ((const int32_t*)bp.ptr[o])[r];
+                break;
+            case PG_T_I64:
+                ((int64_t*)payload_outs.ptr[o])[pos] =
+                    bp.pack_bits && o == 0
+                        ? pv
+                        : ((const int64_t*)bp.ptr[o])[r];
+                break;
+            default:
+                ((double*)payload_outs.ptr[o])[pos] =
+                    ((const double*)bp.ptr[o])[r];
+        }
+    }
+    const unsigned long long* s = acc + (size_t)i * aw;
+    out_dec[pos] = (int64_t)s[0];
+    out_f64[pos] = aw == 4 ? fx128_to_f64(s[2], s[1]) : 0.0;
+    out_cnt[pos] = (int64_t)s[aw - 1];
+}
+
 /* ONE pass per block: count the block's chunk (first sweep, lines land
  * in L2), reserve a contiguous span with one atomicAdd, then emit into
  * it (second sweep hits L2).  Group output order is block-interleaved —
@@ -3243,48 +3411,32 @@ __global__ __launch_bounds__(256) void k_groups_emit(
         for (int w = 0; w < wid; w++) woff += wcnt[w];
         if (sel) {
             int64_t pos = woff + __popcll(m & ((1ull << lane) - 1));
-            /* range-group tables store no keys: the slot index IS key-1 */
-            int64_t kw = keys ? keys[i] : i + 1;
-            out_key[pos] = bp.pack_bits ? (kw >> bp.pack_bits) : kw;
-            int64_t r = bp.by_slot ? i : (int64_t)head[i];
-            for (int o = 0; o < bp.n; o++) {
-                int64_t pv = bp.pack_bits && o == 0
-                                 ? (kw & ((1ll << bp.pack_bits) - 1))
-                                 : 0;
-                switch (bp.tag[o]) {
-                    case PG_T_U8:
-                        ((uint8_t*)payload_outs.ptr[o])[pos] =
-                            bp.pack_bits && o == 0
-                                ? (uint8_t)pv
-                                : ((const uint8_t*)bp.ptr[o])[r];
-                        break;
-                    case PG_T_I32:
-                        ((int32_t*)payload_outs.ptr[o])[pos] =
-                            bp.pack_bits && o == 0
-                                ? (int32_t)pv
-                                : ((const int32_t*)bp.ptr[o])[r];
-                        break;
-                    case PG_T_I64:
-                        ((int64_t*)payload_outs.ptr[o])[pos] =
-                            bp.pack_bits && o == 0
-                                ? pv
-                                : ((const int64_t*)bp.ptr[o])[r];
-                        break;
-                    default:
-                        ((double*)payload_outs.ptr[o])[pos] =
-                            ((const double*)bp.ptr[o])[r];
-                }
-            }
-            const unsigned long long* s = acc + (size_t)i * aw;
-            out_dec[pos] = (int64_t)s[0];
-            out_f64[pos] = aw == 4 ? fx128_to_f64(s[2], s[1]) : 0.0;
-            out_cnt[pos] = (int64_t)s[aw - 1];
+            d_group_row(keys, head, acc, aw, bp, i, pos, out_key,
+                        payload_outs, out_dec, out_f64, out_cnt);
         }
         __syncthreads();
         if (threadIdx.x == 0)
             running += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
         __syncthreads();
     }
+}
+
+/* the same rows from the table's hit list: entry i names the slot of
+ * output row i, so there is no scan, no cursor and no second pass — one
+ * key line and one accumulator line gathered per group.  Row order is the
+ * probes' append order (unspecified, as above). */
+__global__ __launch_bounds__(256) void k_groups_emit_list(
+    const void* hits, int32_t wide, int64_t n_hits, const int64_t* keys,
+    const int32_t* head, const unsigned long long* acc, int32_t aw,
+    build_payloads bp, int64_t* out_key, emit_outs payload_outs,
+    int64_t* out_dec, double* out_f64, int64_t* out_cnt)
+{
+    int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos >= n_hits) return;
+    int64_t i = wide ? ((const int64_t*)hits)[pos]
+                     : (int64_t)((const uint32_t*)hits)[pos];
+    d_group_row(keys, head, acc, aw, bp, i, pos, out_key, payload_outs,
+                out_dec, out_f64, out_cnt);
 }
 
 /* ------------------------------------------------------------------ */
@@ -4478,6 +4630,16 @@ struct Table {
     DevBuf keys, head, next, tags;
     DevBuf acc; /* per-slot accumulators, acc_words u64 each */
     int32_t acc_words = 0; /* 4 = [dec, flo, fhi, cnt]; 2 = [dec, cnt] */
+    /* hit list: the slots whose count went 0 -> 1 since acc was last
+     * zeroed, appended by the mode-1 probes (n_rows entries, u32 while
+     * cap <= 2^32) so that finish() gathers the groups instead of
+     * sweeping acc.  Trusted (list_ok) only while every kernel that added
+     * into acc since then also appended. */
+    DevBuf hits, hits_n;    /* entries; device cursor (one u64) */
+    int64_t hits_cap = 0;   /* entries allocated */
+    unsigned long long hits_n_host = 0; /* cursor as of the last probe */
+    bool use_hits = true;   /* PG_GROUPS_LIST=0 at build creation: never */
+    bool list_ok = false;
     DevBuf acc_multi; /* multi-agg probes: acc_stride u64 per slot
                          (n_acc+1 unpacked; fewer when acc_pack) */
     int32_t n_acc = 0;
@@ -4495,6 +4657,28 @@ struct Table {
     std::vector<DevBuf> payload;
     std::vector<int32_t> ptag;
 };
+
+/* acc has just been zeroed (queued on g_stream): the hit list starts over
+ * and is trusted again */
+static void hits_restart(Table* t)
+{
+    if (!t->hits.p) return;
+    CHKV(hipMemsetAsync(t->hits_n.p, 0, 8, g_stream));
+    t->hits_n_host = 0;
+    t->list_ok = true;
+}
+
+static hit_list hits_arg(const Table* t)
+{
+    hit_list hl{};
+    if (t->list_ok) {
+        hl.ents = t->hits.p;
+        hl.cursor = (unsigned long long*)t->hits_n.p;
+        hl.cap = t->hits_cap;
+        hl.wide = t->cap > (1ll << 32);
+    }
+    return hl;
+}
 
 static std::mutex g_mu;
 static std::map<int64_t, std::unique_ptr<Table>> g_tables;
@@ -5132,6 +5316,9 @@ struct BuildOp : Op {
     {
         t.reset(new Table());
         t->key_set_only = plan.key_set_only != 0;
+        /* PG_GROUPS_LIST=0 keeps group extraction on the accumulator scan */
+        if (const char* eg = getenv("PG_GROUPS_LIST"))
+            t->use_hits = atoi(eg) != 0;
         /* the single-scan builds evaluate comparisons only (see
          * d_eval_preds); chained builds filter through the selection
          * path, which knows the null tests */
@@ -5790,6 +5977,7 @@ struct JoinOp : Op {
                 t->acc_multi.zero();
                 CHKV(hipStreamSynchronize(g_stream));
             }
+            t->list_ok = false; /* k_probe_agg_multi does not append */
         } else if (plan.mode == 1) {
             /* slim 2-word accumulators when this consumer reads only the
              * tick sum + count (dec_only / dec_min) — halves the zeroing
@@ -5800,6 +5988,19 @@ struct JoinOp : Op {
                 t->acc_words = want_aw;
                 t->acc.alloc((size_t)t->cap * t->acc_words * 8);
                 t->acc.zero();
+                /* the hit list is born with the zeroed accumulators.
+                 * Groups <= inserted build rows, so n_rows entries hold
+                 * every first touch; no zeroing needed.  Range-group
+                 * tables hit most of their range and keep the scan. */
+                if (t->use_hits && !t->range_group) {
+                    t->hits_cap = t->n_rows;
+                    t->hits.alloc((size_t)t->hits_cap *
+                                  (t->cap > (1ll << 32) ? 8 : 4));
+                    t->hits_n.alloc(8);
+                    t->hits_n.zero();
+                    t->hits_n_host = 0;
+                    t->list_ok = true;
+                }
                 CHKV(hipStreamSynchronize(g_stream));
             } else if (want_aw == 4 && t->acc_words == 2) {
                 throw std::runtime_error(
@@ -5813,6 +6014,7 @@ struct JoinOp : Op {
             hipLaunchKernelGGL(k_acc_min_init, dim3(2048), dim3(256), 0,
                                g_stream, (unsigned long long*)t->acc.p,
                                t->acc_words, t->cap);
+            hits_restart(t); /* every count is zero again */
             CHKV(hipStreamSynchronize(g_stream));
         }
         if (plan.mode == 2) {
@@ -5851,6 +6053,7 @@ struct JoinOp : Op {
                 t2->acc.zero();
                 CHKV(hipStreamSynchronize(g_stream));
             }
+            t2->list_ok = false; /* k_probe_agg_pay does not append */
         }
     }
     void add_input(const pg_page* in) override
@@ -5903,6 +6106,7 @@ struct JoinOp : Op {
             return;
         }
         if (plan.mode == 3) {
+            t2->list_ok = false; /* also after a reset since construction */
             hot_begin();
             hipLaunchKernelGGL(k_probe_agg_pay, dim3(4096), dim3(256), 0,
                                g_stream, sp.pg, plan,
@@ -5976,7 +6180,7 @@ struct JoinOp : Op {
                     (const uint8_t*)t->tags.p, t->mask, t->local_mask,
                     t->pack_bits, (const unsigned long long*)t->kbits.p, t->bmax, plan.dec_only,
                     (unsigned long long*)t->acc.p, t->acc_words,
-                    (unsigned long long*)ovf.p);
+                    (unsigned long long*)ovf.p, hits_arg(t));
             } else {
                 hipLaunchKernelGGL(k_probe_agg, dim3(4096), dim3(256), 0,
                                    g_stream, sp.pg, plan,
@@ -5986,9 +6190,14 @@ struct JoinOp : Op {
                                    (const unsigned long long*)t->kbits.p, t->bmax,
                                    (unsigned long long*)t->acc.p,
                                    t->acc_words,
-                                   (unsigned long long*)ovf.p);
+                                   (unsigned long long*)ovf.p, hits_arg(t));
             }
             hot_end();
+            /* the list count rides on this page's synchronise, so that
+             * finish() can size and launch the extraction without one */
+            if (t->list_ok)
+                CHKV(hipMemcpyAsync(&t->hits_n_host, t->hits_n.p, 8,
+                                    hipMemcpyDeviceToHost, g_stream));
             CHKV(hipStreamSynchronize(g_stream));
             return;
         }
@@ -6197,6 +6406,54 @@ struct JoinOp : Op {
         sel_emit(bpg, fp, nullptr, 0, chunk, r, outs);
         outq.push_back(std::move(op));
     }
+    /* the groups page of t from its hit list: columns as in the scan
+     * path (key, payloads, dec, f64, cnt), sized at the list count;
+     * queues k_groups_emit_list and does not synchronise */
+    void extract_by_list(OutPage& op)
+    {
+        const int64_t total = (int64_t)t->hits_n_host;
+        op.pg.n_rows = total;
+        int nc = 0;
+        auto add_dev_col = [&](int tag) {
+            op.dev.emplace_back();
+            op.dev.back().alloc((size_t)total * type_size(tag));
+            op.pg.cols[nc].tag = tag;
+            op.pg.cols[nc].on_device = 1;
+            op.pg.cols[nc].data = op.dev.back().p;
+            return nc++;
+        };
+        int c_key = add_dev_col(PG_T_I64);
+        build_payloads bp{};
+        bp.n = (int32_t)t->payload.size();
+        bp.by_slot = t->slot_payloads ? 1 : 0;
+        bp.pack_bits = t->pack_bits;
+        emit_outs pl_outs{};
+        pl_outs.n = bp.n;
+        for (int o = 0; o < bp.n; o++) {
+            bp.ptr[o] = t->payload[o].p;
+            bp.tag[o] = t->ptag[o];
+            int c = add_dev_col(t->ptag[o]);
+            pl_outs.ptr[o] = op.pg.cols[c].data;
+            pl_outs.tag[o] = t->ptag[o];
+        }
+        int c_dec = add_dev_col(PG_T_I64);
+        int c_f64 = add_dev_col(PG_T_F64);
+        int c_cnt = add_dev_col(PG_T_I64);
+        op.pg.n_cols = nc;
+        if (total == 0) return;
+        hipLaunchKernelGGL(k_groups_emit_list,
+                           dim3((unsigned)((total + 255) / 256)), dim3(256),
+                           0, g_stream, (const void*)t->hits.p,
+                           (int32_t)(t->cap > (1ll << 32)), total,
+                           (const int64_t*)t->keys.p,
+                           (const int32_t*)t->head.p,
+                           (const unsigned long long*)t->acc.p,
+                           t->acc_words, bp,
+                           (int64_t*)op.pg.cols[c_key].data, pl_outs,
+                           (int64_t*)op.pg.cols[c_dec].data,
+                           (double*)op.pg.cols[c_f64].data,
+                           (int64_t*)op.pg.cols[c_cnt].data);
+    }
     void finish() override
     {
         if (marking()) {
@@ -6242,9 +6499,24 @@ struct JoinOp : Op {
             return;
         }
         if (plan.mode != 1 && plan.mode != 3) return;
+        /* list extraction (mode 1, single aggregate): gather the slots
+         * the probes first touched.  One key line and one accumulator
+         * line per group against one sweep of the accumulator array: an
+         * all-keys-hit probe of a well-filled table stays on the scan.
+         * The kernel is queued ahead of the overflow read-back, whose
+         * synchronise is then the only one of this finish(). */
+        OutPage lop;
+        const bool by_list =
+            plan.mode == 1 && plan.n_aggs == 0 && t->list_ok &&
+            !t->range_group && t->hits_n_host <= (uint64_t)t->hits_cap &&
+            (double)t->hits_n_host * 128.0 <
+                (double)t->cap * t->acc_words * 8.0;
+        if (by_list) extract_by_list(lop);
         {
             unsigned long long h_ovf[2] = {0, 0};
-            CHKV(hipMemcpy(h_ovf, ovf.p, 16, hipMemcpyDeviceToHost));
+            CHKV(hipMemcpyAsync(h_ovf, ovf.p, 16, hipMemcpyDeviceToHost,
+                                g_stream));
+            CHKV(hipStreamSynchronize(g_stream));
             if (h_ovf[0])
                 throw std::runtime_error(
                     "bigint/decimal SUM overflow in grouped probe "
@@ -6255,6 +6527,11 @@ struct JoinOp : Op {
                     "SUM_F64 addend outside the exact fixed-point domain "
                     "in grouped probe (needs 0 <= x < 2^53 with no "
                     "fraction bits below 2^-64)");
+        }
+        if (by_list) {
+            g_groups_list_extractions++;
+            outq.push_back(std::move(lop));
+            return;
         }
         /* extract groups: slots with count>0, slot-ascending (mode 3
          * groups live in table2) */
@@ -7527,8 +7804,10 @@ extern "C" pg_status pg_table_reset_acc(int64_t t)
                 return seterr("pg_table_reset_acc: table not found");
             tbl = it->second.get();
         }
-        if (tbl->acc.p)
+        if (tbl->acc.p) {
             CHK(hipMemsetAsync(tbl->acc.p, 0, tbl->acc.sz, g_stream));
+            hits_restart(tbl);
+        }
         if (tbl->acc_multi.p)
             CHK(hipMemsetAsync(tbl->acc_multi.p, 0, tbl->acc_multi.sz,
                                g_stream));
