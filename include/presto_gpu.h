@@ -114,15 +114,21 @@ typedef struct {
                                  PG_CMP_IS_NULL / PG_CMP_IS_NOT_NULL test
                                  the mask itself; projections and
                                  aggregate inputs read the values array
-                                 as is.  Output pages carry masks only
+                                 as is, except in GROUPBY_MULTI with
+                                 sql_nulls = 1, whose group keys and
+                                 SUM / MIN / MAX inputs honor the masks
+                                 (see pg_plan_groupby).  Output pages
+                                 carry masks only
                                  out of the outer LOOKUP_JOIN modes
                                  (PG_JOIN_PROBE_OUTER and up: null-padded
                                  payloads, gathered probe-column masks,
-                                 the drain page) and out of ORDER_BY
+                                 the drain page), out of ORDER_BY
                                  (gathered masks of emitted columns, and
-                                 its keys honor theirs) and out of WINDOW
+                                 its keys honor theirs), out of WINDOW
                                  (the same, plus the masks of its SUM,
-                                 MIN, MAX, LAG and LEAD columns); every
+                                 MIN, MAX, LAG and LEAD columns) and out
+                                 of GROUPBY_MULTI with sql_nulls = 1 (its
+                                 key and SUM / MIN / MAX columns); every
                                  other operator emits null_mask = NULL.
                                  A mask follows
                                  its column: host for host columns,
@@ -570,7 +576,49 @@ typedef struct {
      * row count; groups emitted slot-ascending (order is not part of
      * the contract, as with the reference's parallel drivers).
      * capacity_hint must be >= the number of distinct groups (errors
-     * out past fill 0.85, like agg tables). */
+     * out past fill 0.85, like agg tables).
+     *
+     * sql_nulls (the last field): 0 = the behaviour above, in which key
+     * channels and aggregate inputs read the values array as is and the
+     * output carries no masks; 1 = SQL null semantics, below; any other
+     * value fails pg_op_create with an error naming sql_nulls.
+     *   - Row predicates preds[0..n_preds) are unchanged: a null
+     *     excludes the row, IS_NULL / IS_NOT_NULL test the mask.
+     *   - Group keys: a key channel is null at row i when its column has
+     *     a null_mask and null_mask[i] != 0 (for a dictionary VARBIN key
+     *     that is the per-position mask).  Null groups with null in that
+     *     channel (IS NOT DISTINCT FROM) and is distinct from every
+     *     value; the value stored under a null never influences
+     *     grouping.  Channels are independent: (null, 1), (0, 1),
+     *     (null, null) and (0, null) are four groups.  Grouping stays
+     *     exact: the per-channel null flags are one more word of the
+     *     compared key vector, never part of a fingerprint.
+     *   - COUNT stays count(*) over the rows that pass the row
+     *     predicates and its own FILTER; its proj is ignored (a zeroed
+     *     proj is NOT count(col 0)).  count(x) is spelled
+     *     COUNT FILTER (x IS NOT NULL).
+     *   - SUM_DEC, SUM_I64, SUM_F64, MIN, MAX: the input is null when
+     *     any column the projection reads is null at that row (IDENT,
+     *     SHR, SUBDIV read a; DISC_PRICE, MUL, DIV, KEYSHL, KEYSHL_DIV
+     *     read a and b; CHARGE reads a, b and c; constants held in b or
+     *     c are not columns).  A null input is skipped before it is
+     *     evaluated, so the bits under a mask reach neither the overflow
+     *     check, the SUM_F64 domain check nor the accumulator.  A group
+     *     in which an aggregate received no non-null input (all inputs
+     *     null, its FILTER rejected every row, or both) emits null for
+     *     it.  A non-null input of value 0 is an input: a group of zeros
+     *     sums to 0, not null.  Overflow and SUM_F64 domain errors apply
+     *     to the non-null inputs as with sql_nulls = 0.
+     *   - The trailing row count is unchanged: the rows of the group
+     *     that passed the row predicates.
+     *   - Output masks: every key column and every SUM / MIN / MAX
+     *     column carries a device null_mask of n_rows bytes, owned by
+     *     the output page (valid until the next pg_op_get_output /
+     *     pg_op_destroy); the value under a null is 0.  COUNT columns
+     *     and the row count have null_mask = NULL.
+     *   - Out of scope: HASH_AGG_SMALL and the fused aggregating probes
+     *     (LOOKUP_JOIN modes 1-3) keep reading values as is; F64 and
+     *     I128 group keys and signed SUM_F64 stay unsupported. */
     int32_t n_preds;
     pg_pred preds[PG_MAX_PRED];
     int32_t n_keys;
@@ -579,6 +627,7 @@ typedef struct {
     int32_t n_aggs;
     pg_agg aggs[6];
     int32_t agg_filter[6];
+    int32_t sql_nulls;
 } pg_plan_groupby;
 
 typedef struct {

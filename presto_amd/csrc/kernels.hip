@@ -429,6 +429,34 @@ __device__ inline int64_t d_eval_proj_dec(const pg_page& pg, const pg_agg& ag,
     return v * (100 + t);
 }
 
+/* SQL nullness of a projection's input at row i: null when any COLUMN the
+ * kind reads is null there.  The one place that knows which of a, b, c are
+ * channels: IDENT, SHR and SUBDIV read a (their b, c are constants);
+ * DISC_PRICE, MUL, DIV, KEYSHL and KEYSHL_DIV read a and b; CHARGE reads
+ * all three. */
+__device__ inline bool d_col_is_null(const pg_page& pg, int32_t col,
+                                     int64_t i)
+{
+    const uint8_t* m = pg.cols[col].null_mask;
+    return m && m[i];
+}
+__device__ inline bool d_proj_is_null(const pg_page& pg, const pg_proj& p,
+                                      int64_t i)
+{
+    bool n = d_col_is_null(pg, p.a, i);
+    switch (p.kind) {
+        case PG_PROJ_IDENT:
+        case PG_PROJ_SHR:
+        case PG_PROJ_SUBDIV:
+            return n;
+        case PG_PROJ_CHARGE:
+            n = d_col_is_null(pg, p.c, i) || n;
+            [[fallthrough]];
+        default:
+            return d_col_is_null(pg, p.b, i) || n;
+    }
+}
+
 /* deterministic wave butterfly sum (order fixed: x_i += x_{i^s}) */
 __device__ inline double d_bfly_f64(double v)
 {
@@ -3082,6 +3110,12 @@ __global__ __launch_bounds__(256) void k_groups_emit_multi(
 /* "sc1 payload -> vmcnt(0) -> sc1 flag" handoff form, so readers      */
 /* need no acquire fences), and losers compare the full key vector —  */
 /* never a fingerprint approximation.                                  */
+/* SQL_NULLS (pg_plan_groupby.sql_nulls = 1) instantiates the null-     */
+/* aware variant: the key vector grows by one word of per-channel null  */
+/* bits (kv plane n_keys, published and compared like the key words;    */
+/* key words under a null are 0 and fold NULL_HASH_CODE = 0), and each  */
+/* slot carries one word of "aggregate a received input" bits in front  */
+/* of the row count.  SQL_NULLS = false compiles all of that out.       */
 /* ------------------------------------------------------------------ */
 struct gb_agg_off {
     int32_t off[6];
@@ -3096,6 +3130,7 @@ __device__ inline int64_t d_gb_key(const pg_page& pg, int32_t col,
     return d_load_i64(c, i);
 }
 
+template <bool SQL_NULLS>
 __global__ __launch_bounds__(256) void k_groupby_multi(
     pg_page pg, pg_plan_groupby plan, unsigned int* state, int64_t* kv,
     int64_t cap, int64_t mask, unsigned long long* acc, int32_t acc_words,
@@ -3108,10 +3143,19 @@ __global__ __launch_bounds__(256) void k_groupby_multi(
     for (; i < pg.n_rows; i += stride) {
         if (!d_eval_preds(pg, plan.preds, plan.n_preds, i)) continue;
         int64_t k[4];
+        int64_t knull = 0; /* SQL_NULLS: bit ch = channel ch is null */
         uint64_t h = 0;
 #pragma unroll
         for (int ch = 0; ch < 4; ch++) {
             if (ch >= n_keys) break;
+            if constexpr (SQL_NULLS) {
+                if (d_col_is_null(pg, plan.key_col[ch], i)) {
+                    k[ch] = 0; /* the stored value never groups */
+                    knull |= (int64_t)1 << ch;
+                    h = 31u * h; /* NULL_HASH_CODE = 0 */
+                    continue;
+                }
+            }
             k[ch] = d_gb_key(pg, plan.key_col[ch], i);
             h = 31u * h + pg_bigint_hash(k[ch]);
         }
@@ -3130,6 +3174,11 @@ __global__ __launch_bounds__(256) void k_groupby_multi(
                                    __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_SYSTEM) == k[ch];
                 }
+                if constexpr (SQL_NULLS)
+                    eq = eq && __hip_atomic_load(
+                                   &kv[(size_t)n_keys * cap + pos],
+                                   __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_SYSTEM) == knull;
                 if (eq) {
                     slot = pos;
                     break;
@@ -3149,6 +3198,10 @@ __global__ __launch_bounds__(256) void k_groupby_multi(
                                            k[ch], __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_SYSTEM);
                     }
+                    if constexpr (SQL_NULLS)
+                        __hip_atomic_store(&kv[(size_t)n_keys * cap + pos],
+                                           knull, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_SYSTEM);
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     __hip_atomic_store(&state[pos], 2u, __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_SYSTEM);
@@ -3164,6 +3217,7 @@ __global__ __launch_bounds__(256) void k_groupby_multi(
         }
         if (slot < 0) continue;
         unsigned long long* s = acc + (size_t)slot * acc_words;
+        unsigned long long got = 0; /* SQL_NULLS: aggregates fed by row i */
 #pragma unroll
         for (int a = 0; a < 6; a++) {
             if (a >= plan.n_aggs) break;
@@ -3171,6 +3225,14 @@ __global__ __launch_bounds__(256) void k_groupby_multi(
             if (f >= 0 && !d_eval_preds(pg, &plan.preds[f], 1, i))
                 continue;
             unsigned long long* w = s + offs.off[a];
+            if constexpr (SQL_NULLS) {
+                /* COUNT is count(*): its proj is never read.  A null
+                 * input is skipped before it is evaluated. */
+                if (plan.aggs[a].func != PG_AGG_COUNT) {
+                    if (d_proj_is_null(pg, plan.aggs[a].proj, i)) continue;
+                    got |= 1ull << a;
+                }
+            }
             switch (plan.aggs[a].func) {
                 case PG_AGG_COUNT:
                     atomicAdd(w, 1ull);
@@ -3199,6 +3261,16 @@ __global__ __launch_bounds__(256) void k_groupby_multi(
                 }
             }
         }
+        if constexpr (SQL_NULLS) {
+            /* "received input" bits, word acc_words - 2.  They only go
+             * 0 -> 1, so a relaxed load that already shows them set makes
+             * the atomic redundant (the steady state of a group). */
+            unsigned long long* gw = s + acc_words - 2;
+            if (got &&
+                (__hip_atomic_load(gw, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT) & got) != got)
+                atomicOr(gw, got);
+        }
         atomicAdd(s + acc_words - 1, 1ull);
     }
 }
@@ -3224,12 +3296,17 @@ __global__ __launch_bounds__(256) void k_gb_acc_init(
 }
 
 /* groupby extraction: occupied slots (cnt>0) slot-ascending; keys
- * re-narrowed to their input tags, aggregate columns per layout */
+ * re-narrowed to their input tags, aggregate columns per layout.
+ * SQL_NULLS also writes the masks: key_masks.ptr[ch] from the null-bits
+ * plane, agg_masks.ptr[a] (SUM / MIN / MAX; NULL for COUNT) from the
+ * "received input" bits, and 0 for every value under a null. */
+template <bool SQL_NULLS>
 __global__ __launch_bounds__(256) void k_groupby_emit(
     const int64_t* kv, int64_t cap, int32_t n_keys,
     const unsigned long long* acc, int32_t acc_words, gb_agg_off offs,
     pg_plan_groupby plan, int64_t chunk, unsigned long long* cursor,
-    emit_outs key_outs, emit_outs agg_outs)
+    emit_outs key_outs, emit_outs agg_outs, emit_outs key_masks,
+    emit_outs agg_masks)
 {
     const int64_t lo = (int64_t)blockIdx.x * chunk;
     const int64_t hi = min(lo + chunk, cap);
@@ -3276,7 +3353,25 @@ __global__ __launch_bounds__(256) void k_groupby_emit(
                 }
             }
             const unsigned long long* s = acc + (size_t)i * acc_words;
+            if constexpr (SQL_NULLS) {
+                /* key words under a null were stored as 0 */
+                const int64_t knull = kv[(size_t)n_keys * cap + i];
+                for (int ch = 0; ch < n_keys; ch++)
+                    ((uint8_t*)key_masks.ptr[ch])[pos] =
+                        (uint8_t)((knull >> ch) & 1);
+            }
             for (int a = 0; a < plan.n_aggs; a++) {
+                if constexpr (SQL_NULLS) {
+                    if (plan.aggs[a].func != PG_AGG_COUNT) {
+                        const bool isnull =
+                            !((s[acc_words - 2] >> a) & 1ull);
+                        ((uint8_t*)agg_masks.ptr[a])[pos] = isnull;
+                        if (isnull) { /* not the MIN/MAX identity */
+                            ((int64_t*)agg_outs.ptr[a])[pos] = 0;
+                            continue;
+                        }
+                    }
+                }
                 if (plan.aggs[a].func == PG_AGG_SUM_F64)
                     ((double*)agg_outs.ptr[a])[pos] =
                         fx128_to_f64(s[offs.off[a] + 1], s[offs.off[a]]);
@@ -6667,6 +6762,7 @@ struct GroupByOp : Op {
     int64_t cap = 0, mask = 0;
     int32_t key_out_tag[4] = {0, 0, 0, 0};
     bool tags_known = false;
+    bool sql = false; /* plan.sql_nulls == 1 */
     void init()
     {
         if (plan.n_keys < 1 || plan.n_keys > 4)
@@ -6678,6 +6774,9 @@ struct GroupByOp : Op {
                 throw std::runtime_error("agg_filter out of range");
         if (plan.capacity_hint < 1)
             throw std::runtime_error("capacity_hint required");
+        if (plan.sql_nulls != 0 && plan.sql_nulls != 1)
+            throw std::runtime_error("groupby sql_nulls must be 0 or 1");
+        sql = plan.sql_nulls == 1;
         cap = next_pow2(plan.capacity_hint * 2 + 16);
         mask = cap - 1;
         int w = 0;
@@ -6685,10 +6784,13 @@ struct GroupByOp : Op {
             offs.off[a] = w;
             w += plan.aggs[a].func == PG_AGG_SUM_F64 ? 2 : 1;
         }
-        acc_words = w + 1; /* + group row count */
+        /* + group row count, always the last word; sql_nulls puts the
+         * "received input" bits in front of it */
+        acc_words = w + (sql ? 2 : 1);
         state.alloc((size_t)cap * 4);
         state.zero();
-        kv.alloc((size_t)cap * 8 * plan.n_keys);
+        /* sql_nulls: one more plane, the per-channel null bits */
+        kv.alloc((size_t)cap * 8 * (plan.n_keys + (sql ? 1 : 0)));
         acc.alloc((size_t)cap * acc_words * 8);
         acc.zero();
         counters.alloc(32); /* [tick ovf, table full, distinct groups,
@@ -6723,8 +6825,9 @@ struct GroupByOp : Op {
         }
         tags_known = true;
         hot_begin();
-        hipLaunchKernelGGL(k_groupby_multi, dim3(4096), dim3(256), 0,
-                           g_stream, sp.pg, plan,
+        hipLaunchKernelGGL(sql ? k_groupby_multi<true>
+                               : k_groupby_multi<false>,
+                           dim3(4096), dim3(256), 0, g_stream, sp.pg, plan,
                            (unsigned int*)state.p, (int64_t*)kv.p, cap,
                            mask, (unsigned long long*)acc.p, acc_words,
                            offs, (unsigned long long*)counters.p);
@@ -6769,22 +6872,34 @@ struct GroupByOp : Op {
             op.pg.cols[nc].data = op.dev.back().p;
             return nc++;
         };
-        emit_outs key_outs{};
-        key_outs.n = plan.n_keys;
+        /* sql_nulls: one byte per group, owned by the page like the
+         * values */
+        auto add_mask = [&](int cx) {
+            op.dev.emplace_back();
+            op.dev.back().alloc((size_t)total + 1);
+            op.pg.cols[cx].null_mask = (const uint8_t*)op.dev.back().p;
+            return op.dev.back().p;
+        };
+        emit_outs key_outs{}, key_masks{};
+        key_outs.n = key_masks.n = plan.n_keys;
         for (int ch = 0; ch < plan.n_keys; ch++) {
             int tag = tags_known ? key_out_tag[ch] : PG_T_I64;
             int cx = add_dev_col(tag);
             key_outs.ptr[ch] = op.pg.cols[cx].data;
             key_outs.tag[ch] = tag;
+            if (sql) key_masks.ptr[ch] = add_mask(cx);
         }
-        emit_outs agg_outs{};
+        emit_outs agg_outs{}, agg_masks{};
         agg_outs.n = plan.n_aggs + 1;
+        agg_masks.n = plan.n_aggs;
         for (int a = 0; a < plan.n_aggs; a++) {
             int tag = plan.aggs[a].func == PG_AGG_SUM_F64 ? PG_T_F64
                                                           : PG_T_I64;
             int cx = add_dev_col(tag);
             agg_outs.ptr[a] = op.pg.cols[cx].data;
             agg_outs.tag[a] = tag;
+            if (sql && plan.aggs[a].func != PG_AGG_COUNT)
+                agg_masks.ptr[a] = add_mask(cx);
         }
         {
             int cx = add_dev_col(PG_T_I64);
@@ -6792,13 +6907,15 @@ struct GroupByOp : Op {
             agg_outs.tag[plan.n_aggs] = PG_T_I64;
         }
         op.pg.n_cols = nc;
-        hipLaunchKernelGGL(k_groupby_emit, dim3(FLT_NB), dim3(256), 0,
+        hipLaunchKernelGGL(sql ? k_groupby_emit<true>
+                               : k_groupby_emit<false>,
+                           dim3(FLT_NB), dim3(256), 0,
                            g_stream, (const int64_t*)kv.p, cap,
                            plan.n_keys,
                            (const unsigned long long*)acc.p, acc_words,
                            offs, plan, chunk,
                            (unsigned long long*)d_cursor.p,
-                           key_outs, agg_outs);
+                           key_outs, agg_outs, key_masks, agg_masks);
         unsigned long long n_out = 0;
         CHKV(hipMemcpyAsync(&n_out, d_cursor.p, 8, hipMemcpyDeviceToHost,
                             g_stream));

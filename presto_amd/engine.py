@@ -117,7 +117,8 @@ class PlanGroupBy(C.Structure):
     _fields_ = [("n_preds", C.c_int32), ("preds", Pred * 8),
                 ("n_keys", C.c_int32), ("key_col", C.c_int32 * 4),
                 ("capacity_hint", C.c_int64), ("n_aggs", C.c_int32),
-                ("aggs", Agg * 6), ("agg_filter", C.c_int32 * 6)]
+                ("aggs", Agg * 6), ("agg_filter", C.c_int32 * 6),
+                ("sql_nulls", C.c_int32)]
 
 
 class PlanTopN(C.Structure):

@@ -23,7 +23,7 @@ from .engine import (
     JOIN_PROBE_OUTER, JOIN_LOOKUP_OUTER, JOIN_FULL_OUTER,
     PROJ_IDENT, PROJ_DISC_PRICE, PROJ_CHARGE, PROJ_MUL, PROJ_DIV,
     PROJ_KEYSHL, PROJ_SUBDIV, PROJ_KEYSHL_DIV,
-    AGG_COUNT, AGG_SUM_F64, AGG_SUM_DEC, AGG_SUM_I64,
+    AGG_COUNT, AGG_SUM_F64, AGG_SUM_DEC, AGG_SUM_I64, AGG_MIN, AGG_MAX,
 )
 
 
@@ -118,6 +118,15 @@ def sum_f64(proj, scale=0):
 
 def sum_i64(proj):
     return Agg(AGG_SUM_I64, proj, 0)
+
+
+def agg_min(proj, scale=0):
+    """MIN over integer ticks (scale 0: the integer column itself)."""
+    return Agg(AGG_MIN, proj, scale)
+
+
+def agg_max(proj, scale=0):
+    return Agg(AGG_MAX, proj, scale)
 
 
 # ---- struct filling ----
@@ -256,11 +265,18 @@ def filter_project(proj, *, preds=(), **fields):
     return _set(p, fields)
 
 
-def group_by(keys, aggs, capacity_hint, *, preds=(), filters=()):
+def group_by(keys, aggs, capacity_hint, *, preds=(), filters=(),
+             sql_nulls=False):
+    """sql_nulls=True: null group keys form groups of their own, SUM / MIN
+    / MAX skip null inputs and emit null for a group without any, and the
+    output carries null masks (pg_plan_groupby in the header).  count()
+    stays count(*); count(x) is (count(), i) with filters[i] =
+    pred_not_null(x)."""
     p = PlanGroupBy()
     p.n_keys = _fill(p.key_col, "key_col", keys)
     p.capacity_hint = capacity_hint
     _aggs(p, preds, filters, aggs)
+    p.sql_nulls = int(sql_nulls)
     return p
 
 
