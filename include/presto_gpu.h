@@ -128,7 +128,9 @@ typedef struct {
                                  (the same, plus the masks of its SUM,
                                  MIN, MAX, LAG and LEAD columns) and out
                                  of GROUPBY_MULTI with sql_nulls = 1 (its
-                                 key and SUM / MIN / MAX columns); every
+                                 key and SUM / MIN / MAX columns) and out
+                                 of MARK_DISTINCT (the masks of emitted
+                                 columns, and its keys honor theirs); every
                                  other operator emits null_mask = NULL.
                                  A mask follows
                                  its column: host for host columns,
@@ -305,6 +307,13 @@ typedef enum {
                                  running and whole-partition aggregates,
                                  LAG / LEAD over PARTITION BY ... ORDER BY
                                  ... (see pg_plan_window) */
+    /* 11 is left unassigned */
+    PG_OP_MARK_DISTINCT = 12, /* MarkDistinctOperator.java +
+                                 MarkDistinctHash.java: a first-occurrence
+                                 marker column over 1..4 key channels; in
+                                 PG_DISTINCT_ONLY mode SELECT DISTINCT and
+                                 DistinctLimitOperator.java (see
+                                 pg_plan_mark_distinct) */
 } pg_op_kind;
 
 #define PG_MAX_PRED 8
@@ -807,6 +816,83 @@ typedef struct {
     pg_win_spec funcs[PG_MAX_WIN_FUNCS];
 } pg_plan_window;
 
+#define PG_DISTINCT_MARK 0 /* every row, plus a trailing marker column */
+#define PG_DISTINCT_ONLY 1 /* the first rows only (DISTINCT / DistinctLimit) */
+
+typedef struct {
+    /* PG_OP_MARK_DISTINCT: for each row, whether it is the first row ever
+     * fed to this operator with its combination of key values —
+     * MarkDistinctOperator.java over MarkDistinctHash.java (a GroupByHash
+     * on the distinct channels whose group id tells a new group from a
+     * known one).  The marker leaves as a U8 column that downstream
+     * aggregates use as their mask: count(DISTINCT x) ... GROUP BY g is
+     * this operator over (g, x) followed by GROUPBY_MULTI over g with
+     * COUNT FILTER (marker = 1), next to any other aggregate.  In
+     * PG_DISTINCT_ONLY mode the operator emits the first rows themselves:
+     * SELECT DISTINCT, and with a limit DistinctLimitOperator.java.
+     *   - Keys: U8, I32, I64 or dictionary VARBIN channels; a dictionary
+     *     key is its dictionary id, under GROUPBY_MULTI's rules (proper
+     *     dictionary, the same one on every page).  Keys are always
+     *     null-aware: a key is null at row i when its column has a
+     *     null_mask and null_mask[i] != 0.  Null equals null per channel
+     *     and differs from every value; channels are independent, so
+     *     (null, 1), (0, 1), (null, null) and (0, null) are four
+     *     combinations; the value stored under a null never matters.
+     *     Equality is exact on the full key vector plus the per-channel
+     *     null bits, never a fingerprint.
+     *   - First occurrence: rows are totally ordered by page order, then
+     *     row index (what ORDER_BY calls input order).  A row is first if
+     *     and only if no earlier row of any page fed to this operator has
+     *     the same combination — exactly, whatever order the GPU's threads
+     *     reach the table in: of several equal rows in one page the lowest
+     *     row index is first, and a combination first seen in one page is
+     *     never first again in a later one.
+     *   - PG_DISTINCT_MARK: every add_input queues exactly one page of the
+     *     same n_rows: the emit_cols columns in that order, copied bit for
+     *     bit, then one U8 marker column (1 = first, 0 = not) without a
+     *     mask.  limit must be 0.
+     *   - PG_DISTINCT_ONLY: the queued page holds only the first rows of
+     *     the input page, in input order: the emit_cols columns, no
+     *     marker.  limit > 0 is DistinctLimit: once `limit` rows have been
+     *     emitted over all pages, the page that reaches the limit is cut
+     *     to fit and the operator finishes itself — needs_input returns 0
+     *     and a later add_input fails as after finish.  limit = 0 is
+     *     unlimited.
+     *   - Emit columns: fixed width (U8, I32, I64, F64, I128).  A key need
+     *     not be emitted and a column may be emitted twice.  An emitted
+     *     column whose input column has a null_mask carries it (copied in
+     *     mark mode, compacted in only mode); otherwise its null_mask is
+     *     NULL.  Output pages are device-resident, owned by the operator
+     *     until the next pg_op_get_output / pg_op_destroy, and can be fed
+     *     raw into another operator.  Input pages are borrowed and may be
+     *     host- or device-resident, also mixed.  A 0-row input page gives
+     *     a 0-row output page with the same columns.  finish queues
+     *     nothing.
+     *   - Capacity: capacity_hint >= 1 is the expected number of distinct
+     *     combinations; the table is sized as GROUPBY_MULTI sizes its own
+     *     (at most 2^31 slots).  When the table fills past the same 0.85
+     *     rule, the add_input that notices fails with an error naming
+     *     capacity_hint, and every later add_input and finish fails the
+     *     same way; the page that failed has been partly inserted.
+     *   - Errors at create, naming MARK_DISTINCT and the field: n_keys
+     *     outside 1..4, n_emit outside 1..16, an unknown mode, a negative
+     *     limit, a non-zero limit in mark mode, capacity_hint < 1, a
+     *     negative column index.  Errors at add_input, naming the entry:
+     *     an index >= n_cols; an F64, I128 or non-dictionary VARBIN key; a
+     *     VARBIN or dictionary emit column; a key or emit type that
+     *     differs from the first page's; more than 2^31-1 rows in one
+     *     page.  A rejected page leaves the operator as it was.
+     *   - Out of scope: F64, I128 and raw VARBIN keys; variable-width emit
+     *     columns; spilling; one table shared between operators. */
+    int64_t capacity_hint;             /* expected distinct combinations */
+    int64_t limit;                     /* only mode: 0 = none */
+    int32_t n_keys;                    /* 1..4 */
+    int32_t key_col[4];
+    int32_t mode;                      /* PG_DISTINCT_MARK / PG_DISTINCT_ONLY */
+    int32_t n_emit;                    /* 1..16 */
+    int32_t emit_cols[16];
+} pg_plan_mark_distinct;
+
 /* ---- operator lifecycle (Operator.java:20-102 analog) ---- */
 typedef int64_t pg_op;
 
@@ -868,8 +954,8 @@ pg_status pg_page_serialize(const pg_page* page /* host cols */,
  * against their own struct sizes at load time. */
 int32_t pg_abi_struct_sizes(int32_t* out, int32_t n);
 /* sizeof the plan struct of an operator kind (every pg_op_kind value,
- * pg_plan_order_by and pg_plan_window included), or -1 for an unknown
- * kind (the unassigned 9 among them). */
+ * pg_plan_order_by, pg_plan_window and pg_plan_mark_distinct included),
+ * or -1 for an unknown kind (the unassigned 9 and 11 among them). */
 int32_t pg_abi_plan_size(int32_t kind);
 /* the order-preserving key transform of PG_OP_ORDER_BY (csrc/sortkey.h,
  * the code k_sort_encode runs on the device): the u64 whose unsigned

@@ -34,5 +34,6 @@ from .engine import (  # noqa: F401
     WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_COUNT, WIN_SUM, WIN_MIN,
     WIN_MAX, WIN_LAG, WIN_LEAD,
     FRAME_RANGE_RUNNING, FRAME_ROWS_RUNNING, FRAME_PARTITION,
+    OP_MARK_DISTINCT, PlanMarkDistinct, DISTINCT_MARK, DISTINCT_ONLY,
 )
 from . import pipelines, plans  # noqa: F401

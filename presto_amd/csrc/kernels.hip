@@ -4066,6 +4066,192 @@ __global__ __launch_bounds__(256) void k_sort_iota(uint32_t* ids, int64_t n)
 }
 
 /* ------------------------------------------------------------------ */
+/* MARK_DISTINCT — MarkDistinctOperator.java / MarkDistinctHash.java   */
+/* and DistinctLimitOperator.java: is this row the first one with its  */
+/* key combination?  The table is GROUPBY_MULTI's null-aware one: a    */
+/* state word per slot, n_keys + 1 key planes (the last holds the      */
+/* per-channel null bits), the same hash fold, finalizer and           */
+/* CAS-claim / publish protocol.  Each slot carries one more u64,       */
+/* `first`: the smallest global row ordinal (rows of all earlier pages  */
+/* + row index) seen for the slot, all ones until one is.  Winning the  */
+/* claim says nothing about being first — a later row of the page may   */
+/* well claim the slot — so launch 1 only lowers `first` and launch 2,  */
+/* strictly after it, marks the row whose ordinal `first` ended up as.  */
+/* The slot each row found is kept per row (slot_of, 4 bytes) so that   */
+/* launch 2 does not probe again.                                       */
+/* ------------------------------------------------------------------ */
+#define MD_NO_SLOT 0xffffffffu /* the table was full: the row has no slot */
+
+__global__ __launch_bounds__(256) void k_mark_distinct_insert(
+    pg_page pg, pg_plan_mark_distinct plan, unsigned int* state, int64_t* kv,
+    int64_t cap, int64_t mask, unsigned long long* first, int64_t base,
+    uint32_t* slot_of, unsigned long long* counters /* [claims, full] */)
+{
+    const int n_keys = plan.n_keys;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < pg.n_rows; i += stride) {
+        int64_t k[4];
+        int64_t knull = 0; /* bit ch = channel ch is null */
+        uint64_t h = 0;
+#pragma unroll
+        for (int ch = 0; ch < 4; ch++) {
+            if (ch >= n_keys) break;
+            if (d_col_is_null(pg, plan.key_col[ch], i)) {
+                k[ch] = 0; /* the stored value never matters */
+                knull |= (int64_t)1 << ch;
+                h = 31u * h; /* NULL_HASH_CODE = 0 */
+                continue;
+            }
+            k[ch] = d_gb_key(pg, plan.key_col[ch], i);
+            h = 31u * h + pg_bigint_hash(k[ch]);
+        }
+        int64_t pos = (int64_t)(pg_murmur3_finalize(h) & (uint64_t)mask);
+        int64_t slot = -1, tries = 0;
+        for (;;) {
+            unsigned int st = __hip_atomic_load(
+                &state[pos], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (st == 2u) {
+                bool eq = true;
+#pragma unroll
+                for (int ch = 0; ch < 4; ch++) {
+                    if (ch >= n_keys) break;
+                    eq = eq && __hip_atomic_load(
+                                   &kv[(size_t)ch * cap + pos],
+                                   __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_SYSTEM) == k[ch];
+                }
+                eq = eq && __hip_atomic_load(&kv[(size_t)n_keys * cap + pos],
+                                             __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_SYSTEM) ==
+                               knull;
+                if (eq) {
+                    slot = pos;
+                    break;
+                }
+                pos = (pos + 1) & mask;
+                if (++tries > mask) {
+                    atomicAdd(counters + 1, 1ull);
+                    break;
+                }
+            } else if (st == 0u) {
+                unsigned int prev = atomicCAS(&state[pos], 0u, 1u);
+                if (prev == 0u) {
+#pragma unroll
+                    for (int ch = 0; ch < 4; ch++) {
+                        if (ch >= n_keys) break;
+                        __hip_atomic_store(&kv[(size_t)ch * cap + pos],
+                                           k[ch], __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_SYSTEM);
+                    }
+                    __hip_atomic_store(&kv[(size_t)n_keys * cap + pos],
+                                       knull, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_SYSTEM);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __hip_atomic_store(&state[pos], 2u, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_SYSTEM);
+                    atomicAdd(counters, 1ull); /* distinct combinations */
+                    slot = pos;
+                    break;
+                }
+                /* lost the claim: retry the same position */
+            }
+            /* st == 1: publisher in flight — retry (as k_groupby_multi) */
+        }
+        slot_of[i] = slot < 0 ? MD_NO_SLOT : (uint32_t)slot;
+        if (slot < 0) continue;
+        /* `first` only falls, so a relaxed load that already shows a
+         * smaller ordinal makes the atomic redundant — always, on every
+         * page after the key's first one */
+        const unsigned long long ord = (unsigned long long)(base + i);
+        if (__hip_atomic_load(&first[slot], __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_AGENT) > ord)
+            atomicMin(&first[slot], ord);
+    }
+}
+
+/* launch 2: first[slot] is final for the page */
+__device__ inline bool d_md_is_first(const uint32_t* slot_of,
+                                     const unsigned long long* first,
+                                     int64_t base, int64_t i)
+{
+    const uint32_t s = slot_of[i];
+    return s != MD_NO_SLOT && first[s] == (unsigned long long)(base + i);
+}
+
+/* mark mode: one marker byte per row */
+__global__ __launch_bounds__(256) void k_mark_distinct_mark(
+    const uint32_t* slot_of, const unsigned long long* first, int64_t base,
+    int64_t n, uint8_t* marker)
+{
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n;
+         i += stride)
+        marker[i] = d_md_is_first(slot_of, first, base, i);
+}
+
+/* only mode, the selection kernels' block-window scheme: block b owns the
+ * 256-aligned row chunk [b*chunk, (b+1)*chunk), a wave one 64-aligned
+ * ballot word of each 256-row window.  The count pass keeps the words and
+ * the per-block totals; after the host's prefix sum over the blocks the
+ * second pass turns the words into the ascending list of the first
+ * n_out marked row ids, which k_sort_gather then reads. */
+__global__ __launch_bounds__(256) void k_mark_distinct_count(
+    const uint32_t* slot_of, const unsigned long long* first, int64_t base,
+    int64_t n, int64_t chunk, int64_t* block_counts,
+    unsigned long long* selbits)
+{
+    const int64_t lo = (int64_t)blockIdx.x * chunk;
+    const int64_t hi = min(lo + chunk, n);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    int64_t cnt = 0;
+    for (int64_t wbase = lo + 64 * wid; wbase < hi; wbase += 256) {
+        const int64_t i = wbase + lane;
+        const bool sel = i < hi && d_md_is_first(slot_of, first, base, i);
+        const uint64_t m = d_ballot(sel);
+        if (lane == 0) {
+            cnt += __popcll(m);
+            selbits[wbase >> 6] = m;
+        }
+    }
+    __shared__ int64_t lds[4];
+    if (lane == 0) lds[wid] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        block_counts[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
+}
+
+__global__ __launch_bounds__(256) void k_mark_distinct_rowids(
+    const unsigned long long* selbits, int64_t n, int64_t chunk,
+    const int64_t* block_offs, int64_t n_out, uint32_t* rowid)
+{
+    const int64_t lo = (int64_t)blockIdx.x * chunk;
+    const int64_t hi = min(lo + chunk, n);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    __shared__ int64_t wcnt[4];
+    __shared__ int64_t running;
+    if (threadIdx.x == 0) running = block_offs[blockIdx.x];
+    __syncthreads();
+    for (int64_t base = lo; base < hi; base += 256) {
+        const int64_t wbase = base + 64 * wid;
+        /* a wave past the chunk's end has no word of its own */
+        const uint64_t m = wbase < hi ? selbits[wbase >> 6] : 0;
+        if (lane == 0) wcnt[wid] = __popcll(m);
+        __syncthreads();
+        int64_t woff = running;
+        for (int w = 0; w < wid; w++) woff += wcnt[w];
+        if ((m >> lane) & 1) {
+            const int64_t pos = woff + __popcll(m & ((1ull << lane) - 1));
+            if (pos < n_out) rowid[pos] = (uint32_t)(wbase + lane);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            running += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();
+    }
+}
+
+/* ------------------------------------------------------------------ */
 /* WINDOW — WindowOperator.java over the sorted PagesIndex: what runs */
 /* after the sort.  Boundary flags from the keys of adjacent sorted   */
 /* rows, per-row partition / peer-group bounds from scans of the head */
@@ -7715,6 +7901,282 @@ struct WindowOp : SortedInputOp {
     }
 };
 
+/* ---------------- MARK_DISTINCT ---------------- */
+struct MarkDistinctOp : Op {
+    pg_plan_mark_distinct plan;
+    DevBuf state, kv, first, counters;
+    int64_t cap = 0, mask = 0;
+    int64_t rows_seen = 0; /* global ordinal of the next page's row 0 */
+    int64_t emitted = 0;   /* only mode: rows emitted so far */
+    int key_tag[4], emit_tag[16]; /* the first page's */
+    bool typed = false;
+    std::string failed; /* a full table fails every later call the same */
+
+    static std::string fname(const char* field, int i)
+    {
+        return std::string("MARK_DISTINCT: ") + field + "[" +
+               std::to_string(i) + "]";
+    }
+    void init()
+    {
+        if (plan.n_keys < 1 || plan.n_keys > 4)
+            throw std::runtime_error("MARK_DISTINCT: n_keys must be 1..4");
+        if (plan.n_emit < 1 || plan.n_emit > 16)
+            throw std::runtime_error("MARK_DISTINCT: n_emit must be 1..16");
+        if (plan.mode != PG_DISTINCT_MARK && plan.mode != PG_DISTINCT_ONLY)
+            throw std::runtime_error(
+                "MARK_DISTINCT: mode must be PG_DISTINCT_MARK or "
+                "PG_DISTINCT_ONLY");
+        if (plan.limit < 0)
+            throw std::runtime_error("MARK_DISTINCT: limit must be >= 0");
+        if (plan.limit != 0 && plan.mode == PG_DISTINCT_MARK)
+            throw std::runtime_error(
+                "MARK_DISTINCT: limit must be 0 in PG_DISTINCT_MARK mode");
+        if (plan.capacity_hint < 1)
+            throw std::runtime_error(
+                "MARK_DISTINCT: capacity_hint must be >= 1");
+        if (plan.capacity_hint > (1ll << 30) - 8)
+            throw std::runtime_error(
+                "MARK_DISTINCT: capacity_hint needs more than 2^31 slots");
+        for (int i = 0; i < plan.n_keys; i++)
+            if (plan.key_col[i] < 0)
+                throw std::runtime_error(fname("key_col", i) +
+                                         " is negative");
+        for (int i = 0; i < plan.n_emit; i++)
+            if (plan.emit_cols[i] < 0)
+                throw std::runtime_error(fname("emit_cols", i) +
+                                         " is negative");
+        cap = next_pow2(plan.capacity_hint * 2 + 16); /* as GROUPBY_MULTI */
+        mask = cap - 1;
+        state.alloc((size_t)cap * 4);
+        state.zero();
+        kv.alloc((size_t)cap * 8 * (plan.n_keys + 1));
+        first.alloc((size_t)cap * 8);
+        CHKV(hipMemsetAsync(first.p, 0xff, (size_t)cap * 8, g_stream));
+        counters.alloc(16); /* [claims, table full] */
+        counters.zero();
+    }
+    /* every check before the first copy: a rejected page leaves the
+     * operator as it was */
+    void check(const pg_page* in)
+    {
+        if (in->n_rows < 0)
+            throw std::runtime_error("MARK_DISTINCT: n_rows < 0");
+        if (in->n_rows > INT32_MAX)
+            throw std::runtime_error("MARK_DISTINCT: more than 2^31-1 rows "
+                                     "in one page (row ids are 32-bit)");
+        auto col_of = [&](const std::string& name, int c) -> const pg_col& {
+            if (c >= in->n_cols)
+                throw std::runtime_error(
+                    name + " = " + std::to_string(c) +
+                    " is not a column of the page (n_cols " +
+                    std::to_string(in->n_cols) + ")");
+            return in->cols[c];
+        };
+        auto same = [&](const std::string& name, int tag, int first_tag) {
+            if (typed && tag != first_tag)
+                throw std::runtime_error(
+                    name + ": type " + std::to_string(tag) +
+                    " differs from the first page's " +
+                    std::to_string(first_tag));
+        };
+        for (int i = 0; i < plan.n_keys; i++) {
+            const std::string name = fname("key_col", i);
+            const pg_col& c = col_of(name, plan.key_col[i]);
+            if (c.tag == PG_T_F64 || c.tag == PG_T_I128)
+                throw std::runtime_error(name + ": F64 and I128 keys are "
+                                                "unsupported");
+            if (c.tag == PG_T_VARBIN && !c.dict_ids)
+                throw std::runtime_error(
+                    name + ": VARBIN keys must be dictionary blocks (the "
+                           "key is the dictionary id)");
+            if (c.tag != PG_T_U8 && c.tag != PG_T_I32 &&
+                c.tag != PG_T_I64 && c.tag != PG_T_VARBIN)
+                throw std::runtime_error(name + ": unknown column type " +
+                                         std::to_string(c.tag));
+            same(name, c.tag, key_tag[i]);
+        }
+        for (int i = 0; i < plan.n_emit; i++) {
+            const std::string name = fname("emit_cols", i);
+            const pg_col& c = col_of(name, plan.emit_cols[i]);
+            if (c.tag == PG_T_VARBIN || c.dict_ids)
+                throw std::runtime_error(name + ": VARBIN and dictionary "
+                                                "columns are unsupported");
+            if (c.tag != PG_T_U8 && c.tag != PG_T_I32 &&
+                c.tag != PG_T_I64 && c.tag != PG_T_F64 &&
+                c.tag != PG_T_I128)
+                throw std::runtime_error(name + ": unknown column type " +
+                                         std::to_string(c.tag));
+            same(name, c.tag, emit_tag[i]);
+        }
+        for (int i = 0; i < plan.n_keys; i++)
+            key_tag[i] = in->cols[plan.key_col[i]].tag;
+        for (int i = 0; i < plan.n_emit; i++)
+            emit_tag[i] = in->cols[plan.emit_cols[i]].tag;
+        typed = true;
+    }
+    /* after the page's kernels have run: did the table fill? */
+    void check_fill(const unsigned long long* c)
+    {
+        if (c[1] || (int64_t)c[0] * 100 > cap * 85) {
+            failed = c[1] ? "MARK_DISTINCT: table full: raise capacity_hint"
+                          : "MARK_DISTINCT: fill exceeded 0.85: raise "
+                            "capacity_hint";
+            throw std::runtime_error(failed);
+        }
+    }
+    void add_input(const pg_page* in) override
+    {
+        if (!failed.empty()) throw std::runtime_error(failed);
+        check(in);
+        const int64_t n = in->n_rows;
+        const bool only = plan.mode == PG_DISTINCT_ONLY;
+        /* the kernels' page: the key columns, in only mode the emit
+         * columns too (the gather reads them on the device); every other
+         * column stays where it is */
+        pg_page need = *in;
+        for (int c = 0; c < need.n_cols; c++) {
+            bool used = false;
+            for (int i = 0; i < plan.n_keys; i++)
+                used = used || plan.key_col[i] == c;
+            for (int i = 0; only && i < plan.n_emit; i++)
+                used = used || plan.emit_cols[i] == c;
+            if (!used) need.cols[c] = pg_col{};
+        }
+        StagedPage sp;
+        sp.stage(&need);
+        const int64_t base = rows_seen;
+        DevBuf slot_of;
+        slot_of.alloc((size_t)n * 4);
+        const int grid = (int)std::min<int64_t>((n + 255) / 256, FT_NBLOCKS);
+        if (n > 0) {
+            hot_begin();
+            hipLaunchKernelGGL(k_mark_distinct_insert, dim3(grid), dim3(256),
+                               0, g_stream, sp.pg, plan,
+                               (unsigned int*)state.p, (int64_t*)kv.p, cap,
+                               mask, (unsigned long long*)first.p, base,
+                               (uint32_t*)slot_of.p,
+                               (unsigned long long*)counters.p);
+            hot_end();
+        }
+        unsigned long long c[2] = {0, 0};
+        OutPage op;
+        op.pg.n_cols = plan.n_emit + (only ? 0 : 1);
+        auto add_col = [&](int cx, int tag, int64_t rows, bool with_mask) {
+            op.dev.emplace_back();
+            op.dev.back().alloc((size_t)rows * type_size(tag));
+            op.pg.cols[cx].tag = tag;
+            op.pg.cols[cx].on_device = 1;
+            op.pg.cols[cx].data = op.dev.back().p;
+            op.pg.cols[cx].null_mask = nullptr;
+            if (with_mask) {
+                op.dev.emplace_back();
+                op.dev.back().alloc((size_t)rows);
+                op.pg.cols[cx].null_mask = (const uint8_t*)op.dev.back().p;
+            }
+        };
+        if (!only) {
+            /* the emit columns as they are, from wherever they are */
+            for (int o = 0; o < plan.n_emit; o++) {
+                const pg_col& src = in->cols[plan.emit_cols[o]];
+                const hipMemcpyKind kind = src.on_device
+                                               ? hipMemcpyDeviceToDevice
+                                               : hipMemcpyHostToDevice;
+                add_col(o, src.tag, n, src.null_mask != nullptr);
+                if (n > 0) {
+                    CHKV(hipMemcpyAsync(op.pg.cols[o].data, src.data,
+                                        (size_t)n * type_size(src.tag), kind,
+                                        g_stream));
+                    if (src.null_mask)
+                        CHKV(hipMemcpyAsync((void*)op.pg.cols[o].null_mask,
+                                            src.null_mask, (size_t)n, kind,
+                                            g_stream));
+                }
+            }
+            add_col(plan.n_emit, PG_T_U8, n, false);
+            if (n > 0)
+                hipLaunchKernelGGL(k_mark_distinct_mark, dim3(grid),
+                                   dim3(256), 0, g_stream,
+                                   (const uint32_t*)slot_of.p,
+                                   (const unsigned long long*)first.p, base,
+                                   n, (uint8_t*)op.pg.cols[plan.n_emit].data);
+            CHKV(hipMemcpyAsync(c, counters.p, 16, hipMemcpyDeviceToHost,
+                                g_stream));
+            CHKV(hipStreamSynchronize(g_stream));
+            check_fill(c);
+            op.pg.n_rows = n;
+        } else {
+            const int64_t chunk = sel_chunk(n);
+            DevBuf d_counts, selbits, d_offs, rowid;
+            std::vector<int64_t> h(FLT_NB, 0);
+            if (n > 0) {
+                d_counts.alloc(FLT_NB * sizeof(int64_t));
+                selbits.alloc(((size_t)(n + 255) / 256 * 4 + 1) * 8);
+                hipLaunchKernelGGL(k_mark_distinct_count, dim3(FLT_NB),
+                                   dim3(256), 0, g_stream,
+                                   (const uint32_t*)slot_of.p,
+                                   (const unsigned long long*)first.p, base,
+                                   n, chunk, (int64_t*)d_counts.p,
+                                   (unsigned long long*)selbits.p);
+                CHKV(hipMemcpyAsync(h.data(), d_counts.p, FLT_NB * 8,
+                                    hipMemcpyDeviceToHost, g_stream));
+            }
+            CHKV(hipMemcpyAsync(c, counters.p, 16, hipMemcpyDeviceToHost,
+                                g_stream));
+            CHKV(hipStreamSynchronize(g_stream));
+            check_fill(c);
+            int64_t total = 0;
+            for (int b = 0; b < FLT_NB; b++) {
+                const int64_t cnt = h[b];
+                h[b] = total; /* the block's offset */
+                total += cnt;
+            }
+            int64_t n_out = total;
+            if (plan.limit > 0 && emitted + total >= plan.limit) {
+                /* DistinctLimit: cut to fit, and no more input */
+                n_out = plan.limit - emitted;
+                finished = true;
+            }
+            emitted += n_out;
+            sort_gather_cols g{};
+            g.n = plan.n_emit;
+            for (int o = 0; o < plan.n_emit; o++) {
+                const pg_col& src = sp.pg.cols[plan.emit_cols[o]];
+                add_col(o, src.tag, n_out, src.null_mask != nullptr);
+                g.src[o] = src.data;
+                g.dst[o] = op.pg.cols[o].data;
+                g.width[o] = (int)type_size(src.tag);
+                g.msrc[o] = src.null_mask;
+                g.mdst[o] = (uint8_t*)op.pg.cols[o].null_mask;
+            }
+            if (n_out > 0) {
+                rowid.alloc((size_t)n_out * 4);
+                d_offs.alloc(FLT_NB * sizeof(int64_t));
+                CHKV(hipMemcpyAsync(d_offs.p, h.data(), FLT_NB * 8,
+                                    hipMemcpyHostToDevice, g_stream));
+                hipLaunchKernelGGL(k_mark_distinct_rowids, dim3(FLT_NB),
+                                   dim3(256), 0, g_stream,
+                                   (const unsigned long long*)selbits.p, n,
+                                   chunk, (const int64_t*)d_offs.p, n_out,
+                                   (uint32_t*)rowid.p);
+                const int ggrid =
+                    (int)std::min<int64_t>((n_out + 255) / 256, 2048);
+                hipLaunchKernelGGL(k_sort_gather, dim3(ggrid), dim3(256), 0,
+                                   g_stream, (const uint32_t*)rowid.p, n_out,
+                                   g);
+                CHKV(hipStreamSynchronize(g_stream));
+            }
+            op.pg.n_rows = n_out;
+        }
+        rows_seen += n;
+        outq.push_back(std::move(op));
+    }
+    void finish() override
+    {
+        if (!failed.empty()) throw std::runtime_error(failed);
+    }
+};
+
 /* shared_ptr so a concurrent pg_op_destroy cannot free an Op another
  * thread's call still holds (each C-ABI entry copies the ref; the
  * per-handle single-threaded contract of presto_gpu.h still applies to
@@ -7805,6 +8267,15 @@ extern "C" pg_status pg_op_create(int32_t kind, const void* plan,
                 if (plan_bytes != sizeof(pg_plan_window))
                     return seterr("bad plan size");
                 auto* o = new WindowOp();
+                op.reset(o);
+                memcpy(&o->plan, plan, sizeof(o->plan));
+                o->init();
+                break;
+            }
+            case PG_OP_MARK_DISTINCT: {
+                if (plan_bytes != sizeof(pg_plan_mark_distinct))
+                    return seterr("bad plan size");
+                auto* o = new MarkDistinctOp();
                 op.reset(o);
                 memcpy(&o->plan, plan, sizeof(o->plan));
                 o->init();
@@ -8436,6 +8907,8 @@ extern "C" int32_t pg_abi_plan_size(int32_t kind)
         case PG_OP_GROUPBY_MULTI: return (int32_t)sizeof(pg_plan_groupby);
         case PG_OP_ORDER_BY: return (int32_t)sizeof(pg_plan_order_by);
         case PG_OP_WINDOW: return (int32_t)sizeof(pg_plan_window);
+        case PG_OP_MARK_DISTINCT:
+            return (int32_t)sizeof(pg_plan_mark_distinct);
         default: return -1;
     }
 }

@@ -27,6 +27,9 @@ JOIN_INNER, JOIN_PROBE_OUTER, JOIN_LOOKUP_OUTER, JOIN_FULL_OUTER = 0, 4, 5, 6
 (OP_FILTER_PROJECT, OP_HASH_AGG_SMALL, OP_HASH_BUILD, OP_LOOKUP_JOIN,
  OP_TOPN, OP_PARTITION, OP_GROUPBY_MULTI, OP_ORDER_BY) = range(1, 9)
 OP_WINDOW = 10  # 9 is left unassigned
+OP_MARK_DISTINCT = 12  # 11 is left unassigned
+# pg_plan_mark_distinct.mode (PG_DISTINCT_*)
+DISTINCT_MARK, DISTINCT_ONLY = 0, 1
 # pg_sort_order (SortOrder.java)
 (SORT_ASC_NULLS_FIRST, SORT_ASC_NULLS_LAST, SORT_DESC_NULLS_FIRST,
  SORT_DESC_NULLS_LAST) = range(4)
@@ -148,6 +151,13 @@ class PlanWindow(C.Structure):
                 ("key_col", C.c_int32 * 4), ("order", C.c_int32 * 4),
                 ("n_emit", C.c_int32), ("emit_cols", C.c_int32 * 16),
                 ("n_funcs", C.c_int32), ("funcs", WinSpec * 8)]
+
+
+class PlanMarkDistinct(C.Structure):
+    _fields_ = [("capacity_hint", C.c_int64), ("limit", C.c_int64),
+                ("n_keys", C.c_int32), ("key_col", C.c_int32 * 4),
+                ("mode", C.c_int32), ("n_emit", C.c_int32),
+                ("emit_cols", C.c_int32 * 16)]
 
 
 class _Lib:

@@ -13,7 +13,7 @@ import ctypes as C
 from .engine import (
     Pred, Proj, Agg, PlanFilterProject, PlanHashAggSmall, PlanHashBuild,
     PlanLookupJoin, PlanGroupBy, PlanTopN, PlanPartition, PlanOrderBy,
-    PlanWindow, WinSpec,
+    PlanWindow, WinSpec, PlanMarkDistinct, DISTINCT_MARK, DISTINCT_ONLY,
     WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_COUNT, WIN_SUM, WIN_MIN,
     WIN_MAX, WIN_LAG, WIN_LEAD,
     FRAME_RANGE_RUNNING, FRAME_ROWS_RUNNING, FRAME_PARTITION,
@@ -370,6 +370,38 @@ def window(partition_by, order_by, emit, funcs):
     if p.n_funcs == 0:
         raise ValueError("funcs: WINDOW needs at least one function")
     return p
+
+
+def _mark_distinct(mode, keys, emit, capacity, limit):
+    p = PlanMarkDistinct()
+    p.n_keys = _fill(p.key_col, "key_col", keys)
+    p.n_emit = _fill(p.emit_cols, "emit_cols", emit)
+    if p.n_keys == 0:
+        raise ValueError("key_col: MARK_DISTINCT needs at least one key")
+    if p.n_emit == 0:
+        raise ValueError("emit_cols: MARK_DISTINCT needs at least one "
+                         "column")
+    p.mode = mode
+    p.capacity_hint = capacity
+    p.limit = limit
+    return p
+
+
+def mark_distinct(keys, emit, capacity):
+    """First-occurrence marker over the key channels: every input page
+    comes back as its `emit` channels plus a trailing U8 column, 1 on the
+    first row ever seen with its key combination (null is a value).
+    capacity is the expected number of distinct combinations.
+    count(DISTINCT x) GROUP BY g is mark_distinct([g, x], ...) feeding
+    group_by([g], [(count(), 0)], filters=[pred(marker, CMP_EQ, 1)])."""
+    return _mark_distinct(DISTINCT_MARK, keys, emit, capacity, 0)
+
+
+def distinct(keys, emit, capacity, limit=0):
+    """SELECT DISTINCT: only the first row of every key combination, in
+    input order, as the `emit` channels; limit > 0 stops after that many
+    rows (DistinctLimit), after which the operator takes no more input."""
+    return _mark_distinct(DISTINCT_ONLY, keys, emit, capacity, limit)
 
 
 def partition(n_partitions, key_col, emit):
