@@ -100,7 +100,16 @@ typedef enum {
                         EQ/NE/CONTAINS/PREFIX predicates, hashing/
                         partitioning (XxHash64 per
                         AbstractVariableWidthBlock.java:102-105) and
-                        IDENT projection/emit (two-pass gather). */
+                        IDENT projection/emit (two-pass gather).
+                        Emit is implemented by FILTER_PROJECT only: every
+                        other emitting operator (PARTITION, all LOOKUP_JOIN
+                        emit modes, ORDER_BY, WINDOW, MARK_DISTINCT)
+                        rejects a variable-width or dictionary emit column
+                        at add_input, naming the entry.  One output column
+                        holds at most 2^31-1 bytes (32-bit offsets);
+                        FILTER_PROJECT fails with an error naming the
+                        column beyond that.  A host column whose strings
+                        are all empty may pass data = NULL. */
 } pg_type;
 
 typedef struct {
@@ -192,7 +201,20 @@ typedef struct {
     double dval;   /* compare value for f64 columns */
     char sval[40]; /* VARBIN: compare bytes (EQ/NE/CONTAINS/PREFIX;
                       CONTAINS2 packs both patterns) */
-    int32_t slen;
+    int32_t slen;  /* LENGTH RULES, checked at pg_op_create by every
+                      operator that carries preds[] (the error names the
+                      operator, the predicate index and the field):
+                      0 <= slen <= sizeof sval; for CONTAINS2 and
+                      NOT_CONTAINS2 also 0 <= ival and
+                      slen + ival <= sizeof sval.  An empty needle matches
+                      everywhere.  IS_NULL / IS_NOT_NULL ignore both.
+                      TYPE RULES, checked at pg_op_add_input where the
+                      column types are known (the error names the
+                      predicate index): the ordering ops LT/LE/GT/GE are
+                      not defined for VARBIN columns, and CONTAINS,
+                      PREFIX, CONTAINS2 and NOT_CONTAINS2 are defined for
+                      VARBIN columns only; a rejected page leaves the
+                      operator as it was. */
     int32_t rhs_col; /* 0: compare against the constant; k>0: compare
                         against integer channel k-1 PLUS the constant
                         (col OP col + ival / dval — e.g. Q5's
@@ -653,9 +675,12 @@ typedef struct {
     int32_t key_col; /* bigint; rawHash = CombineHashFunction fold from
                         INITIAL_HASH_VALUE=0 of AbstractLongType.hash
                         (PlannerUtils.java:113, AbstractLongType.java:137-140);
-                        partition = HashGenerator.java:22-29 */
+                        partition = HashGenerator.java:22-29.  A VARBIN
+                        (raw or dictionary) key hashes its bytes with
+                        XxHash64.  The key's null_mask is NOT read:
+                        partitioning null keys is out of scope */
     int32_t n_emit;
-    int32_t emit_cols[8];
+    int32_t emit_cols[8]; /* fixed-width columns only (see PG_T_VARBIN) */
 } pg_plan_partition;
 
 #define PG_MAX_SORT_KEYS 4

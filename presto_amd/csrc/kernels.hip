@@ -4828,6 +4828,82 @@ static size_t type_size(int tag)
     }
 }
 
+/* ---- host checks of a plan's predicates ----
+ * d_eval_preds trusts what it is given: it indexes sval by slen (and by
+ * ival for the second needle) and picks its arm by the column's tag alone.
+ * These two checks keep a foreign caller from reaching it with a plan the
+ * kernels would answer silently wrong.  Both are plain loops over at most
+ * PG_MAX_PRED predicates: no launch, no sync. */
+
+/* the entries of preds[] a plan reads, one bit each: the row filter
+ * preds[0..n_preds) plus any per-aggregate FILTER */
+static uint32_t preds_used(int32_t n_preds,
+                           const int32_t* agg_filter = nullptr,
+                           int32_t n_aggs = 0)
+{
+    uint32_t used = 0;
+    for (int p = 0; p < n_preds && p < PG_MAX_PRED; p++) used |= 1u << p;
+    for (int a = 0; a < n_aggs && a < 6; a++)
+        if (agg_filter[a] >= 0 && agg_filter[a] < PG_MAX_PRED)
+            used |= 1u << agg_filter[a];
+    return used;
+}
+
+/* at create: needle lengths inside sval */
+static void check_pred_lens(const char* opname, const pg_pred* preds,
+                            uint32_t used)
+{
+    const int64_t cap = (int64_t)sizeof(preds[0].sval);
+    for (int p = 0; p < PG_MAX_PRED; p++) {
+        if (!(used >> p & 1)) continue;
+        const pg_pred& pr = preds[p];
+        if (pr.op >= PG_CMP_IS_NULL) continue; /* reads the mask alone */
+        if (pr.slen < 0 || pr.slen > cap)
+            throw std::runtime_error(
+                std::string(opname) + ": preds[" + std::to_string(p) +
+                "].slen = " + std::to_string(pr.slen) + " is outside 0.." +
+                std::to_string(cap) + " (the size of sval)");
+        if ((pr.op == PG_CMP_CONTAINS2 || pr.op == PG_CMP_NOT_CONTAINS2) &&
+            (pr.ival < 0 || pr.ival > cap - pr.slen))
+            throw std::runtime_error(
+                std::string(opname) + ": preds[" + std::to_string(p) +
+                "].ival = " + std::to_string(pr.ival) +
+                " (the second needle's length) must be >= 0 and fit sval "
+                "after the first needle's " + std::to_string(pr.slen) +
+                " of " + std::to_string(cap) + " bytes");
+    }
+}
+
+/* at add_input, where the column types are known: ordering comparisons are
+ * not defined for VARBIN, the string ops for nothing else */
+static void check_pred_types(const char* opname, const pg_pred* preds,
+                             uint32_t used, const pg_page* in)
+{
+    for (int p = 0; p < PG_MAX_PRED; p++) {
+        if (!(used >> p & 1)) continue;
+        const pg_pred& pr = preds[p];
+        if (pr.op >= PG_CMP_IS_NULL) continue; /* any column type */
+        if (pr.col < 0 || pr.col >= in->n_cols || pr.col >= 32) continue;
+        const bool varbin = in->cols[pr.col].tag == PG_T_VARBIN;
+        const bool ordering = pr.op >= PG_CMP_LT && pr.op <= PG_CMP_GE;
+        const bool string_op =
+            pr.op >= PG_CMP_CONTAINS && pr.op <= PG_CMP_NOT_CONTAINS2;
+        if (varbin && ordering)
+            throw std::runtime_error(
+                std::string(opname) + ": preds[" + std::to_string(p) +
+                "] is an ordering comparison (op " + std::to_string(pr.op) +
+                ") on VARBIN column " + std::to_string(pr.col) +
+                "; LT/LE/GT/GE are not defined for variable-width columns");
+        if (!varbin && string_op)
+            throw std::runtime_error(
+                std::string(opname) + ": preds[" + std::to_string(p) +
+                "] is a string op (" + std::to_string(pr.op) +
+                ": CONTAINS/PREFIX/CONTAINS2/NOT_CONTAINS2) on fixed-width "
+                "column " + std::to_string(pr.col) +
+                "; it needs a VARBIN column");
+    }
+}
+
 /* stage a (possibly host-resident) page onto the device; staged buffers
  * live for the duration of one call (input pages are borrowed) */
 struct StagedPage {
@@ -4837,18 +4913,30 @@ struct StagedPage {
     {
         pg = *in;
         for (int c = 0; c < in->n_cols; c++) {
-            if (!in->cols[c].data) continue;
-            if (in->cols[c].tag == PG_T_VARBIN && !in->cols[c].on_device) {
+            /* a host VARBIN column whose strings are all empty may come
+             * with a NULL byte buffer: its offsets, ids and mask are staged
+             * all the same */
+            const bool host_varbin = in->cols[c].tag == PG_T_VARBIN &&
+                                     !in->cols[c].on_device;
+            if (!in->cols[c].data && !(host_varbin && in->cols[c].offsets))
+                continue;
+            if (host_varbin) {
                 /* bytes buffer + offsets (n_rows+1, or dict_n+1 for
                  * dictionary blocks) + optional dict ids */
                 const int32_t* ho = in->cols[c].offsets;
                 int64_t n_elem = in->cols[c].dict_ids ? in->cols[c].dict_n
                                                       : in->n_rows;
                 size_t nb = (size_t)ho[n_elem];
+                if (nb && !in->cols[c].data)
+                    throw std::runtime_error(
+                        "VARBIN column " + std::to_string(c) +
+                        ": data is NULL but its offsets span " +
+                        std::to_string(nb) + " bytes");
                 bufs.emplace_back();
                 bufs.back().alloc(nb ? nb : 1);
-                CHKV(hipMemcpyAsync(bufs.back().p, in->cols[c].data, nb,
-                                    hipMemcpyHostToDevice, g_stream));
+                if (nb)
+                    CHKV(hipMemcpyAsync(bufs.back().p, in->cols[c].data, nb,
+                                        hipMemcpyHostToDevice, g_stream));
                 pg.cols[c].data = bufs.back().p;
                 bufs.emplace_back();
                 bufs.back().alloc(((size_t)n_elem + 1) * 4);
@@ -5070,8 +5158,15 @@ static void sel_emit(const pg_page& pg, const pg_plan_filter_project& plan,
 /* ---------------- FILTER_PROJECT ---------------- */
 struct FilterOp : Op {
     pg_plan_filter_project plan;
+    void init()
+    {
+        check_pred_lens("FILTER_PROJECT", plan.preds,
+                        preds_used(plan.n_preds));
+    }
     void add_input(const pg_page* in) override
     {
+        check_pred_types("FILTER_PROJECT", plan.preds,
+                         preds_used(plan.n_preds), in);
         StagedPage sp;
         sp.stage(in);
         const Table* semi = nullptr;
@@ -5137,8 +5232,16 @@ struct FilterOp : Op {
             CHKV(hipStreamSynchronize(g_stream));
             std::vector<int32_t> h_offs(r.n + 1);
             h_offs[0] = 0;
-            for (int64_t j = 0; j < r.n; j++)
-                h_offs[j + 1] = h_offs[j] + h_len[j];
+            int64_t total_bytes = 0; /* offsets are 32-bit: checked below */
+            for (int64_t j = 0; j < r.n; j++) {
+                total_bytes += h_len[j];
+                if (total_bytes > INT32_MAX)
+                    throw std::runtime_error(
+                        "FILTER_PROJECT: VARBIN output column " +
+                        std::to_string(o) + " exceeds 2^31-1 bytes (32-bit "
+                        "offsets); feed smaller pages");
+                h_offs[j + 1] = (int32_t)total_bytes;
+            }
             op.dev.emplace_back(); /* offsets */
             op.dev.back().alloc(((size_t)r.n + 1) * 4);
             void* offs_p = op.dev.back().p;
@@ -5175,6 +5278,8 @@ struct AggSmallOp : Op {
     {
         if (plan.n_aggs < 1 || plan.n_aggs >= PG_MAX_AGG)
             throw std::runtime_error("n_aggs must be in [1, 7]");
+        check_pred_lens("HASH_AGG_SMALL", plan.preds,
+                        preds_used(plan.n_preds));
         user_aggs = plan.n_aggs;
         /* internal presence count */
         pg_agg cnt{};
@@ -5353,6 +5458,8 @@ struct AggSmallOp : Op {
     }
     void add_input(const pg_page* in) override
     {
+        check_pred_types("HASH_AGG_SMALL", plan.preds,
+                         preds_used(plan.n_preds), in);
         StagedPage sp;
         sp.stage(in);
         hot_begin();
@@ -5595,6 +5702,7 @@ struct BuildOp : Op {
     }
     void init()
     {
+        check_pred_lens("HASH_BUILD", plan.preds, preds_used(plan.n_preds));
         t.reset(new Table());
         t->key_set_only = plan.key_set_only != 0;
         /* PG_GROUPS_LIST=0 keeps group extraction on the accumulator scan */
@@ -5789,6 +5897,8 @@ struct BuildOp : Op {
             throw std::runtime_error(
                 "range_group tables take no build input (the domain is "
                 "the key range itself)");
+        check_pred_types("HASH_BUILD", plan.preds, preds_used(plan.n_preds),
+                         in);
         StagedPage sp;
         sp.stage(in);
         /* resolve payload tags on first page (payload 0 is u8 when it
@@ -6159,8 +6269,16 @@ struct JoinOp : Op {
     {
         return tb->ptag[o] >= 0 ? tb->ptag[o] : PG_T_I64;
     }
+    /* the row filter, plus the per-aggregate FILTERs of a multi-agg probe */
+    uint32_t used_preds() const
+    {
+        return plan.mode == 1 && plan.n_aggs > 0
+                   ? preds_used(plan.n_preds, plan.agg_filter, plan.n_aggs)
+                   : preds_used(plan.n_preds);
+    }
     void init()
     {
+        check_pred_lens("LOOKUP_JOIN", plan.preds, used_preds());
         std::lock_guard<std::mutex> lk(g_mu);
         auto it = g_tables.find(plan.table);
         if (it == g_tables.end())
@@ -6339,6 +6457,20 @@ struct JoinOp : Op {
     }
     void add_input(const pg_page* in) override
     {
+        check_pred_types("LOOKUP_JOIN", plan.preds, used_preds(), in);
+        /* the emit joins copy fixed-width probe columns only (VARBIN emit
+         * is FILTER_PROJECT's two-pass gather): refuse before any launch */
+        if (emit_mode())
+            for (int o = 0; o < plan.n_emit && o < 8; o++) {
+                const int32_t ec = plan.emit_probe_cols[o];
+                if (ec >= 0 && ec < in->n_cols &&
+                    in->cols[ec].tag == PG_T_VARBIN)
+                    throw std::runtime_error(
+                        std::string(outer() ? "outer " : "") +
+                        "LOOKUP_JOIN emits fixed-width probe columns only: "
+                        "emit_probe_cols[" + std::to_string(o) +
+                        "] is VARBIN column " + std::to_string(ec));
+            }
         StagedPage sp;
         sp.stage(in);
         if (plan.mode == 2) {
@@ -6484,17 +6616,10 @@ struct JoinOp : Op {
         }
         /* emit mode: per-block count -> host scan -> prefix emit */
         int64_t n = sp.pg.n_rows;
-        if (outer()) {
+        if (outer() && probe_tags.empty())
             for (int o = 0; o < plan.n_emit; o++)
-                if (sp.pg.cols[plan.emit_probe_cols[o]].tag == PG_T_VARBIN)
-                    throw std::runtime_error(
-                        "outer LOOKUP_JOIN emits fixed-width probe "
-                        "columns only");
-            if (probe_tags.empty())
-                for (int o = 0; o < plan.n_emit; o++)
-                    probe_tags.push_back(
-                        sp.pg.cols[plan.emit_probe_cols[o]].tag);
-        }
+                probe_tags.push_back(
+                    sp.pg.cols[plan.emit_probe_cols[o]].tag);
         if (n == 0) { /* empty probe page -> empty output page */
             OutPage op;
             op.pg.n_rows = 0;
@@ -6958,6 +7083,9 @@ struct GroupByOp : Op {
         for (int a = 0; a < plan.n_aggs; a++)
             if (plan.agg_filter[a] >= PG_MAX_PRED)
                 throw std::runtime_error("agg_filter out of range");
+        check_pred_lens("GROUPBY_MULTI", plan.preds,
+                        preds_used(plan.n_preds, plan.agg_filter,
+                                   plan.n_aggs));
         if (plan.capacity_hint < 1)
             throw std::runtime_error("capacity_hint required");
         if (plan.sql_nulls != 0 && plan.sql_nulls != 1)
@@ -6993,6 +7121,10 @@ struct GroupByOp : Op {
     }
     void add_input(const pg_page* in) override
     {
+        check_pred_types("GROUPBY_MULTI", plan.preds,
+                         preds_used(plan.n_preds, plan.agg_filter,
+                                    plan.n_aggs),
+                         in);
         StagedPage sp;
         sp.stage(in);
         for (int ch = 0; ch < plan.n_keys; ch++) {
@@ -7237,6 +7369,18 @@ struct PartitionOp : Op {
     std::vector<DevBuf> owned; /* partition column buffers; pages alias */
     void add_input(const pg_page* in) override
     {
+        /* the scatter copies fixed-width values (VARBIN emit is
+         * FILTER_PROJECT's two-pass gather): refuse before any launch.  A
+         * VARBIN key is fine: it is hashed, not emitted. */
+        for (int o = 0; o < plan.n_emit && o < 8; o++) {
+            const int32_t ec = plan.emit_cols[o];
+            if (ec >= 0 && ec < in->n_cols &&
+                in->cols[ec].tag == PG_T_VARBIN)
+                throw std::runtime_error(
+                    "PARTITION emits fixed-width columns only: emit_cols[" +
+                    std::to_string(o) + "] is VARBIN column " +
+                    std::to_string(ec));
+        }
         StagedPage sp;
         sp.stage(in);
         int P = plan.n_partitions;
@@ -8198,8 +8342,9 @@ extern "C" pg_status pg_op_create(int32_t kind, const void* plan,
                 if (plan_bytes != sizeof(pg_plan_filter_project))
                     return seterr("bad plan size");
                 auto* o = new FilterOp();
-                memcpy(&o->plan, plan, sizeof(o->plan));
                 op.reset(o);
+                memcpy(&o->plan, plan, sizeof(o->plan));
+                o->init();
                 break;
             }
             case PG_OP_HASH_AGG_SMALL: {

@@ -53,7 +53,9 @@ def pred_varbin(col, op, needle, needle2=None):
     if len(sval) > Pred.sval.size:
         raise ValueError(f"sval: {len(sval)} bytes exceed {Pred.sval.size}")
     p = Pred(col, op, len(needle2 or b""), 0.0)
-    p.sval = sval
+    # not `p.sval = sval`: the c_char array setter stops at the first NUL,
+    # and a needle is bytes, not a C string
+    C.memmove(C.addressof(p) + Pred.sval.offset, sval, len(sval))
     p.slen = len(needle)
     return p
 

@@ -209,53 +209,7 @@ def test_fx128_exact_roundtrip(oracle_lib):
     assert back == float(exact)
 
 
-def _xxh64_py(data, seed=0):
-    """Independent pure-Python restatement of XXH64 (the reference's
-    varchar hash via io.airlift.slice.XxHash64)."""
-    M = (1 << 64) - 1
-    P1, P2, P3 = 0x9E3779B185EBCA87, 0xC2B2AE3D27D4EB4F, 0x165667B19E3779F9
-    P4, P5 = 0x85EBCA77C2B2AE63, 0x27D4EB2F165667C5
-
-    def rotl(x, r):
-        return ((x << r) | (x >> (64 - r))) & M
-
-    def rnd(acc, x):
-        return (rotl((acc + x * P2) & M, 31) * P1) & M
-
-    n = len(data)
-    i = 0
-    if n >= 32:
-        v = [(seed + P1 + P2) & M, (seed + P2) & M, seed,
-             (seed - P1) & M]
-        while i + 32 <= n:
-            for j in range(4):
-                lane = int.from_bytes(data[i:i + 8], "little")
-                v[j] = rnd(v[j], lane)
-                i += 8
-        h = (rotl(v[0], 1) + rotl(v[1], 7) + rotl(v[2], 12) +
-             rotl(v[3], 18)) & M
-        for j in range(4):
-            h = ((h ^ rnd(0, v[j])) * P1 + P4) & M
-    else:
-        h = (seed + P5) & M
-    h = (h + n) & M
-    while i + 8 <= n:
-        h = ((rotl((h ^ rnd(0, int.from_bytes(data[i:i + 8], "little"))) & M,
-                   27) * P1) + P4) & M
-        i += 8
-    if i + 4 <= n:
-        h = ((rotl(h ^ (int.from_bytes(data[i:i + 4], "little") * P1) & M,
-                   23) * P2) + P3) & M
-        i += 4
-    while i < n:
-        h = (rotl(h ^ (data[i] * P5) & M, 11) * P1) & M
-        i += 1
-    h ^= h >> 33
-    h = (h * P2) & M
-    h ^= h >> 29
-    h = (h * P3) & M
-    h ^= h >> 32
-    return h
+from varbin_refs import xxh64 as _xxh64_py  # tests/ is on sys.path
 
 
 def test_xxh64_restatement(oracle_lib):

@@ -207,6 +207,20 @@ def test_q13_two_needle_predicate_bytes():
         pl.pred_varbin(1, P.CMP_CONTAINS, b"x" * 41)
 
 
+def test_varbin_needle_keeps_nul_bytes():
+    """A needle is bytes, not a C string: what follows a NUL must reach
+    sval (the c_char array setter would stop there)."""
+    import ctypes as C
+    p = pl.pred_varbin(0, P.CMP_CONTAINS, b"\x00\xffab\x00c")
+    assert C.string_at(C.addressof(p) + P.Pred.sval.offset, 40) == \
+        b"\x00\xffab\x00c".ljust(40, b"\0")
+    assert p.slen == 6
+    p = pl.pred_varbin(0, P.CMP_CONTAINS2, b"a\x00", b"\x00b")
+    assert C.string_at(C.addressof(p) + P.Pred.sval.offset, 5) == \
+        b"a\x00\x00b\x00"
+    assert (p.slen, p.ival) == (2, 2)
+
+
 def test_q1_small_agg_bytes():
     qty, ep, dc, tx, sd, rf, ls = range(7)
     exp = P.PlanHashAggSmall()
