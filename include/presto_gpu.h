@@ -77,6 +77,10 @@ int64_t pg_build_staged_launches(void);
  * (PG_GROUPS_LIST=0 in the environment at build creation forces the
  * scan) */
 int64_t pg_groups_list_extractions(void);
+/* how many LOOKUP_JOIN probe pages this process has sent through the
+ * multi-key probe kernels (plans with n_keys >= 1) rather than the
+ * single-key ones; an empty page launches nothing and is not counted */
+int64_t pg_multikey_probe_pages(void);
 
 /* ---- Page / Block descriptors (SURVEY.md §8b struct) ----
  * Concrete layouts follow the Java blocks: fixed-width values array +
@@ -449,6 +453,45 @@ typedef struct {
      * nonzero" dense probing; the pipeline accounts for the bias in
      * its downstream predicates. */
     int32_t dense_payload_bias;
+    /* MULTI-CHANNEL JOIN KEYS — the JoinHash / PagesHash analog
+     * (PagesHash.java:81-181, JoinCompiler: a join on any list of hash
+     * channels).  n_keys = 0 (a zero-initialised plan): the single bigint
+     * key_col above, every table shape above, unchanged.  n_keys = 1..4:
+     * a MULTI-KEY CHAINED table over key_cols[0, n_keys), most
+     * significant first; key_col is ignored.
+     *   - Shape: takes preds, semijoin_table / semijoin_col and
+     *     payload_col[] (U8 / I32 / I64 / F64) and nothing else —
+     *     agg_table, dense_array, range_group, key_set_only, pack_bits,
+     *     fill_x10, bitmap_max_key and payload_lookup_table each fail
+     *     pg_op_create with an error naming HASH_BUILD, n_keys and the
+     *     field.  n_keys outside 0..4, or a negative key_cols entry, fails
+     *     create.
+     *   - Key types: U8, I32 or I64 columns, checked at add_input (F64,
+     *     I128, VARBIN and dictionary keys are errors naming the key index
+     *     and the column: ids of two dictionaries are not comparable) and
+     *     the same on every page of one operator.  Each channel compares
+     *     as the signed 64-bit value of the column (U8 zero-extended, I32
+     *     sign-extended), so build and probe channels may differ in width:
+     *     I32 -1 equals I64 -1, U8 255 equals I64 255 and not I32 -1.
+     *     Equality is exact on the whole key vector (never a fingerprint)
+     *     and positional: (1, 2) does not match (2, 1).
+     *   - Null keys (SQL join semantics): a row whose key is null in any
+     *     channel (the column has a null_mask and null_mask[i] != 0)
+     *     matches nothing — null does not equal null here, unlike
+     *     MARK_DISTINCT — and the value under a null never matters.  A
+     *     build row with a null key is kept in the build-row arrays (it
+     *     counts in build-row order and the outer modes drain it) but is
+     *     never inserted into the table.  Build payload masks stay out of
+     *     scope.
+     *   - Build rows are capped at 2^31-1 (row ids are 32-bit): finish
+     *     fails beyond that.
+     *   - The table is probed by LOOKUP_JOIN plans with the same n_keys in
+     *     modes 0, 4, 5 and 6 (see pg_plan_lookup_join), and cannot serve
+     *     as a semijoin_table, payload_lookup_table or table2. */
+    int32_t n_keys;      /* 0: legacy, key_col is the one bigint key;
+                            1..4: multi-key */
+    int32_t key_cols[4]; /* most significant first; only [0, n_keys) are
+                            read */
 } pg_plan_hash_build;
 
 /* pg_plan_lookup_join.mode values of the emit joins (modes 1-3 are the
@@ -583,6 +626,33 @@ typedef struct {
     int32_t acc_pack_width[6];
     int32_t acc_pack_cnt_shift;
     int32_t acc_pack_cnt_width;
+    /* MULTI-CHANNEL JOIN KEYS (see pg_plan_hash_build.n_keys).  n_keys = 0:
+     * key_col above, unchanged.  n_keys = 1..4: the probe key is the
+     * vector key_cols[0, n_keys) of U8 / I32 / I64 columns (checked at
+     * add_input like the build's; the same on every page) and key_col is
+     * ignored.
+     *   - n_keys must equal the table's: a multi-key plan on a legacy
+     *     table, a legacy plan on a multi-key table, or two different
+     *     counts fail pg_op_create with an error naming both counts.
+     *   - Modes 0, 4, 5 and 6 only; modes 1-3 fail create, naming the
+     *     mode.
+     *   - Null probe keys: a probe row whose key is null in any channel
+     *     matches nothing in EVERY mode of the multi-key path — mode 0
+     *     included, which drops the row.  (The legacy mode 0 does not read
+     *     the key mask; no existing plan changes, the path is new.)  Modes
+     *     4 and 6 emit the row null-padded, mode 5 emits nothing.
+     *   - Everything else is the emit contract above word for word: probe
+     *     rows ascending, the order among one probe row's matches
+     *     unpinned, emit_probe_cols then the payloads, the payload mask in
+     *     modes 4 and 6, gathered probe-column masks in modes 4-6, one
+     *     drain page in build-row order across build pages (build rows
+     *     with a null key are never matched, so they drain), marks owned
+     *     by the operator, a 0-row page for an empty probe page, preds
+     *     applied below the join. */
+    int32_t n_keys;      /* 0: legacy, key_col is the one bigint key;
+                            1..4: multi-key */
+    int32_t key_cols[4]; /* most significant first; only [0, n_keys) are
+                            read */
 } pg_plan_lookup_join;
 
 typedef struct {

@@ -171,6 +171,11 @@ extern "C" int64_t pg_groups_list_extractions(void)
 {
     return g_groups_list_extractions;
 }
+static int64_t g_multikey_probe_pages = 0;
+extern "C" int64_t pg_multikey_probe_pages(void)
+{
+    return g_multikey_probe_pages;
+}
 
 /* ------------------------------------------------------------------ */
 /* device helpers                                                     */
@@ -2677,6 +2682,279 @@ __global__ __launch_bounds__(256) void k_probe_emit(
     }
 }
 
+/* ------------------------------------------------------------------ */
+/* Multi-key joins (pg_plan_hash_build.n_keys >= 1): JoinHash /          */
+/* PagesHash over 1..4 hash channels (PagesHash.java:81-181).            */
+/* The build rows keep their widened key vector row-major in key_rows    */
+/* (n_keys int64 per row, written by k_mk_gather in add_input, immutable */
+/* afterwards) plus one "any channel null" byte.  The table is one u64   */
+/* word per slot, (hash >> 32) << 32 | representative build row, all     */
+/* ones = empty (a row id is < 2^31, so no word collides with it).  A    */
+/* claim is ONE CAS that installs the word; whoever meets an occupied    */
+/* slot with the same 32 hash bits compares its key vector against       */
+/* key_rows[rep], which an earlier launch wrote — so no thread ever      */
+/* waits for another (no claim/publish state as in GROUPBY_MULTI).       */
+/* Duplicates hang off the representative: next[i] =                     */
+/* atomicExch(&next[rep], i) on a next[] preset to -1; next[rep] is only */
+/* ever exchanged and next[i] of a duplicate only ever stored by i.      */
+/* A probe miss costs one random line; key_rows is touched only when the */
+/* 32 hash bits agree.  Hash = the group-by's: murmur3 finaliser over    */
+/* the CombineHashFunction fold of the per-channel bigint hashes.        */
+/* ------------------------------------------------------------------ */
+#define MK_EMPTY 0xffffffffffffffffull
+
+struct mk_keys {
+    int32_t n;
+    int32_t col[4];
+};
+
+/* the key vector of row i and its hash; false when a channel is null */
+__device__ inline bool d_mk_load(const pg_page& pg, const mk_keys& mk,
+                                 int64_t i, int64_t* k, uint64_t* h)
+{
+    uint64_t f = 0;
+#pragma unroll
+    for (int ch = 0; ch < 4; ch++) {
+        if (ch >= mk.n) break;
+        if (d_col_is_null(pg, mk.col[ch], i)) return false;
+        k[ch] = d_load_i64(pg.cols[mk.col[ch]], i);
+        f = 31u * f + pg_bigint_hash(k[ch]);
+    }
+    *h = pg_murmur3_finalize(f);
+    return true;
+}
+
+__device__ inline bool d_mk_equal(const int64_t* kr, const int64_t* k, int n)
+{
+    bool eq = true;
+#pragma unroll
+    for (int ch = 0; ch < 4; ch++) {
+        if (ch >= n) break;
+        eq = eq && kr[ch] == k[ch];
+    }
+    return eq;
+}
+
+/* build add_input: widen the key channels of the selected rows (rowid =
+ * their source row indexes, in build-row order) into key_rows / knull */
+__global__ __launch_bounds__(256) void k_mk_gather(
+    pg_page pg, mk_keys mk, const int64_t* rowid, int64_t n,
+    int64_t* key_rows, uint8_t* knull)
+{
+    int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; j < n; j += stride) {
+        const int64_t i = rowid[j];
+        bool isnull = false;
+#pragma unroll
+        for (int ch = 0; ch < 4; ch++) {
+            if (ch >= mk.n) break;
+            const bool nl = d_col_is_null(pg, mk.col[ch], i);
+            isnull = isnull || nl;
+            /* the value under a null never matters: store 0 */
+            key_rows[j * mk.n + ch] =
+                nl ? 0 : d_load_i64(pg.cols[mk.col[ch]], i);
+        }
+        knull[j] = isnull ? 1 : 0;
+    }
+}
+
+/* build finish: slots preset to MK_EMPTY, next[] to -1.  The probe walk is
+ * bounded by the fill rule (cap >= 2n + 16); err counts rows that found no
+ * slot all the same, which finish() turns into an error. */
+__global__ __launch_bounds__(256) void k_mk_insert(
+    const int64_t* key_rows, const uint8_t* knull, int64_t n, int32_t nk,
+    unsigned long long* slots, int32_t* next, int64_t mask,
+    unsigned long long* err)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) {
+        if (knull[i]) continue; /* kept as a build row, never matched */
+        int64_t k[4];
+        uint64_t f = 0;
+#pragma unroll
+        for (int ch = 0; ch < 4; ch++) {
+            if (ch >= nk) break;
+            k[ch] = key_rows[i * nk + ch];
+            f = 31u * f + pg_bigint_hash(k[ch]);
+        }
+        const uint64_t h = pg_murmur3_finalize(f);
+        const unsigned long long tag = h & 0xffffffff00000000ull;
+        const unsigned long long mine = tag | (unsigned long long)i;
+        int64_t s = (int64_t)(h & (uint64_t)mask);
+        int64_t tries = 0;
+        for (;;) {
+            unsigned long long cur = __hip_atomic_load(
+                &slots[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cur == MK_EMPTY) {
+                cur = atomicCAS(&slots[s], MK_EMPTY, mine);
+                if (cur == MK_EMPTY) break; /* i represents its key */
+            }
+            if ((cur & 0xffffffff00000000ull) == tag) {
+                const int64_t rep = (int64_t)(cur & 0xffffffffull);
+                if (d_mk_equal(key_rows + rep * nk, k, nk)) {
+                    next[i] = atomicExch(&next[rep], (int32_t)i);
+                    break;
+                }
+            }
+            s = (s + 1) & mask;
+            if (++tries > mask) {
+                atomicAdd(err, 1ull);
+                break;
+            }
+        }
+    }
+}
+
+/* the representative build row of key vector k, or -1 */
+__device__ inline int64_t d_mk_find(const unsigned long long* slots,
+                                    int64_t mask, const int64_t* key_rows,
+                                    int32_t nk, const int64_t* k, uint64_t h)
+{
+    const unsigned long long tag = h & 0xffffffff00000000ull;
+    int64_t s = (int64_t)(h & (uint64_t)mask);
+    for (int64_t tries = 0; tries <= mask; tries++) {
+        const unsigned long long cur = slots[s];
+        if (cur == MK_EMPTY) return -1;
+        if ((cur & 0xffffffff00000000ull) == tag) {
+            const int64_t rep = (int64_t)(cur & 0xffffffffull);
+            if (d_mk_equal(key_rows + rep * nk, k, nk)) return rep;
+        }
+        s = (s + 1) & mask;
+    }
+    return -1;
+}
+
+/* the probe passes: k_probe_count / k_probe_emit's geometry (per-block
+ * counts, host scan, wave prefix), so the row order is mode 0's.  A null
+ * in any key channel matches nothing in every mode, mode 0 included. */
+template <bool PROBE_OUTER, bool MARK>
+__global__ __launch_bounds__(256) void k_mk_probe_count(
+    pg_page pg, pg_plan_lookup_join plan, const unsigned long long* slots,
+    const int32_t* next, int64_t mask, const int64_t* key_rows,
+    int64_t chunk, int64_t* block_counts)
+{
+    const int64_t n = pg.n_rows;
+    const int64_t lo = (int64_t)blockIdx.x * chunk;
+    const int64_t hi = min(lo + chunk, n);
+    mk_keys mk;
+    mk.n = plan.n_keys;
+    for (int ch = 0; ch < 4; ch++) mk.col[ch] = plan.key_cols[ch];
+    int64_t total = 0;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+        if (!d_eval_preds(pg, plan.preds, plan.n_preds, i)) continue;
+        int64_t k[4];
+        uint64_t h;
+        int64_t rep = -1;
+        if (d_mk_load(pg, mk, i, k, &h))
+            rep = d_mk_find(slots, mask, key_rows, mk.n, k, h);
+        if (rep >= 0) {
+            for (int32_t r = (int32_t)rep; r >= 0; r = next[r]) total++;
+        } else if constexpr (PROBE_OUTER) {
+            total++;
+        }
+    }
+    total = d_bfly_i64(total);
+    __shared__ int64_t lds[4];
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = total;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        block_counts[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
+}
+
+/* payload columns of output row pos: build row r's, or zeros (r < 0) */
+__device__ inline void d_mk_emit_payloads(const build_payloads& bp,
+                                          const emit_outs& build_outs,
+                                          int64_t r, int64_t pos)
+{
+    for (int o = 0; o < bp.n; o++) {
+        switch (bp.tag[o]) {
+            case PG_T_I32:
+                ((int32_t*)build_outs.ptr[o])[pos] =
+                    r < 0 ? 0 : ((const int32_t*)bp.ptr[o])[r];
+                break;
+            case PG_T_I64:
+            case PG_T_F64: /* bit copy */
+                ((int64_t*)build_outs.ptr[o])[pos] =
+                    r < 0 ? 0 : ((const int64_t*)bp.ptr[o])[r];
+                break;
+            default:
+                ((uint8_t*)build_outs.ptr[o])[pos] =
+                    r < 0 ? 0 : ((const uint8_t*)bp.ptr[o])[r];
+        }
+    }
+}
+
+template <bool PROBE_OUTER, bool MARK>
+__global__ __launch_bounds__(256) void k_mk_probe_emit(
+    pg_page pg, pg_plan_lookup_join plan, const unsigned long long* slots,
+    const int32_t* next, int64_t mask, const int64_t* key_rows,
+    int64_t chunk, const int64_t* block_offs, emit_outs probe_outs,
+    build_payloads bp, emit_outs build_outs, outer_outs oo)
+{
+    constexpr bool OUTER = PROBE_OUTER || MARK;
+    const int64_t n = pg.n_rows;
+    const int64_t lo = (int64_t)blockIdx.x * chunk;
+    const int64_t hi = min(lo + chunk, n);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    mk_keys mk;
+    mk.n = plan.n_keys;
+    for (int ch = 0; ch < 4; ch++) mk.col[ch] = plan.key_cols[ch];
+    __shared__ int64_t wcnt[4];
+    __shared__ int64_t running;
+    if (threadIdx.x == 0) running = block_offs[blockIdx.x];
+    __syncthreads();
+    for (int64_t base = lo; base < hi; base += 256) {
+        int64_t i = base + 64 * wid + lane;
+        int64_t rep = -1;
+        int32_t c = 0;
+        if (i < hi && d_eval_preds(pg, plan.preds, plan.n_preds, i)) {
+            int64_t k[4];
+            uint64_t h;
+            if (d_mk_load(pg, mk, i, k, &h))
+                rep = d_mk_find(slots, mask, key_rows, mk.n, k, h);
+            if (rep >= 0) {
+                for (int32_t r = (int32_t)rep; r >= 0; r = next[r]) c++;
+            } else if constexpr (PROBE_OUTER) {
+                c = 1; /* the null-padded row */
+            }
+        }
+        /* wave inclusive prefix of counts (stable row order) */
+        int64_t pre = c;
+        for (int d = 1; d < 64; d <<= 1) {
+            int64_t t = __shfl_up((long long)pre, d, 64);
+            if (lane >= d) pre += t;
+        }
+        int64_t wtotal = __shfl((long long)pre, 63, 64);
+        int64_t excl = pre - c;
+        if (lane == 0) wcnt[wid] = wtotal;
+        __syncthreads();
+        int64_t woff = running;
+        for (int w = 0; w < wid; w++) woff += wcnt[w];
+        int64_t pos = woff + excl;
+        for (int32_t r = (int32_t)rep; r >= 0; r = next[r]) {
+            d_emit_probe_cols<OUTER>(pg, plan, probe_outs, oo, i, pos);
+            d_mk_emit_payloads(bp, build_outs, r, pos);
+            if constexpr (PROBE_OUTER) oo.pay_null[pos] = 0;
+            /* lanes that matched the same build row all store 1: benign */
+            if constexpr (MARK) oo.marks[r] = 1;
+            pos++;
+        }
+        if constexpr (PROBE_OUTER) {
+            if (rep < 0 && c) { /* no match: payloads are null, values 0 */
+                d_emit_probe_cols<OUTER>(pg, plan, probe_outs, oo, i, pos);
+                d_mk_emit_payloads(bp, build_outs, -1, pos);
+                oo.pay_null[pos] = 1;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            running += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();
+    }
+}
+
 /* mode 2: fused probe + dense-dictionary lookup + equality + small-key
  * grouped SUM — the Q5 local-supplier specialization (see presto_gpu.h).
  * Deterministic: exact ticks (order-independent) + fx128 for f64; groups
@@ -5021,6 +5299,13 @@ struct Table {
                                          input page */
     bool slot_payloads = false; /* payloads indexed by slot (agg tables) */
     bool dense = false;          /* dense_array: payload[key-1], no hash */
+    /* multi-key chained tables (n_keys >= 1): keys holds the slot words
+     * (hash bits | representative row), next the duplicate chains (no
+     * head), key_rows n_keys int64 per build row and knull one "any key
+     * channel null" byte per build row */
+    int32_t n_keys = 0;
+    int32_t key_tag[4] = {-1, -1, -1, -1}; /* the first build page's */
+    DevBuf knull;
     /* compacted build-row arrays: key + payloads */
     DevBuf key_rows;
     std::vector<DevBuf> payload;
@@ -5155,6 +5440,56 @@ static void sel_emit(const pg_page& pg, const pg_plan_filter_project& plan,
     CHKV(hipStreamSynchronize(g_stream));
 }
 
+/* the key channels of a multi-key build or probe page: U8 / I32 / I64
+ * columns, typed as on the operator's first page (first_tag[k] < 0 until
+ * one was fed).  Throws before anything is staged or launched. */
+static void check_multikey_cols(const char* opname, int n_keys,
+                                const int32_t* key_cols, const pg_page* in,
+                                const int32_t* first_tag)
+{
+    for (int k = 0; k < n_keys; k++) {
+        const int32_t c = key_cols[k];
+        const std::string name = std::string(opname) + ": key_cols[" +
+                                 std::to_string(k) + "] (column " +
+                                 std::to_string(c) + ")";
+        if (c < 0 || c >= in->n_cols)
+            throw std::runtime_error(
+                name + " is outside the page's " +
+                std::to_string(in->n_cols) + " columns");
+        const pg_col& col = in->cols[c];
+        const char* what = nullptr;
+        if (col.tag == PG_T_VARBIN)
+            what = col.dict_ids ? "a dictionary column (ids of two "
+                                  "dictionaries are not comparable)"
+                                : "a VARBIN column";
+        else if (col.tag == PG_T_F64)
+            what = "an F64 column";
+        else if (col.tag == PG_T_I128)
+            what = "an I128 column";
+        else if (col.tag != PG_T_U8 && col.tag != PG_T_I32 &&
+                 col.tag != PG_T_I64)
+            what = "of an unknown column type";
+        if (what)
+            throw std::runtime_error(name + " is " + what +
+                                     ": join keys are U8, I32 or I64");
+        if (first_tag[k] >= 0 && first_tag[k] != col.tag)
+            throw std::runtime_error(
+                name + ": type " + std::to_string(col.tag) +
+                " differs from the first page's " +
+                std::to_string(first_tag[k]));
+    }
+}
+
+/* a multi-key table keeps slot words where the others keep keys: it serves
+ * multi-key LOOKUP_JOINs only */
+static void reject_multikey(const Table* t, const char* role)
+{
+    if (t && t->n_keys)
+        throw std::runtime_error(
+            std::string("a multi-key (n_keys >= 1) table cannot serve as ") +
+            role);
+}
+
 /* ---------------- FILTER_PROJECT ---------------- */
 struct FilterOp : Op {
     pg_plan_filter_project plan;
@@ -5176,6 +5511,7 @@ struct FilterOp : Op {
             if (it == g_tables.end())
                 throw std::runtime_error("semijoin table not found");
             semi = it->second.get();
+            reject_multikey(semi, "a semijoin_table");
         }
         int64_t chunk = sel_chunk(sp.pg.n_rows);
         SelResult r = sel_count(sp.pg, plan, semi, plan.semijoin_col, chunk);
@@ -5703,6 +6039,37 @@ struct BuildOp : Op {
     void init()
     {
         check_pred_lens("HASH_BUILD", plan.preds, preds_used(plan.n_preds));
+        if (plan.n_keys < 0 || plan.n_keys > 4)
+            throw std::runtime_error(
+                "HASH_BUILD: n_keys must be 0..4, got " +
+                std::to_string(plan.n_keys));
+        if (plan.n_keys >= 1) {
+            /* a multi-key table is a chained one and nothing else */
+            const char* bad =
+                plan.agg_table              ? "agg_table"
+                : plan.dense_array          ? "dense_array"
+                : plan.range_group          ? "range_group"
+                : plan.key_set_only         ? "key_set_only"
+                : plan.pack_bits            ? "pack_bits"
+                : plan.fill_x10             ? "fill_x10"
+                : plan.bitmap_max_key       ? "bitmap_max_key"
+                : plan.payload_lookup_table ? "payload_lookup_table"
+                                            : nullptr;
+            if (bad)
+                throw std::runtime_error(
+                    std::string("HASH_BUILD: n_keys >= 1 builds a multi-key "
+                                "chained table and cannot be combined "
+                                "with ") + bad);
+            for (int k = 0; k < plan.n_keys; k++)
+                if (plan.key_cols[k] < 0)
+                    throw std::runtime_error(
+                        "HASH_BUILD: n_keys = " +
+                        std::to_string(plan.n_keys) + " but key_cols[" +
+                        std::to_string(k) + "] is negative");
+            if (plan.n_payload < 0 || plan.n_payload > 4)
+                throw std::runtime_error(
+                    "HASH_BUILD: n_keys >= 1 takes n_payload 0..4");
+        }
         t.reset(new Table());
         t->key_set_only = plan.key_set_only != 0;
         /* PG_GROUPS_LIST=0 keeps group extraction on the accumulator scan */
@@ -5852,23 +6219,35 @@ struct BuildOp : Op {
             return;
         }
         cap_rows = plan.capacity_hint > 16 ? plan.capacity_hint : 16;
-        t->key_rows.alloc((size_t)cap_rows * 8);
+        t->n_keys = plan.n_keys;
+        t->key_rows.alloc((size_t)cap_rows * 8 * key_words());
+        if (plan.n_keys) t->knull.alloc((size_t)cap_rows);
         for (int i = 0; i < plan.n_payload; i++) {
             t->payload.emplace_back();
             t->ptag.push_back(-1); /* resolved on first input */
             t->payload.back().alloc((size_t)cap_rows * 8);
         }
     }
+    /* int64 words of key_rows per build row */
+    size_t key_words() const { return plan.n_keys ? plan.n_keys : 1; }
     void grow(int64_t need)
     {
         if (need <= cap_rows) return;
         int64_t nc = cap_rows;
         while (nc < need) nc *= 2;
         DevBuf nk;
-        nk.alloc((size_t)nc * 8);
-        CHKV(hipMemcpyAsync(nk.p, t->key_rows.p, (size_t)t->n_rows * 8,
+        nk.alloc((size_t)nc * 8 * key_words());
+        CHKV(hipMemcpyAsync(nk.p, t->key_rows.p,
+                            (size_t)t->n_rows * 8 * key_words(),
                             hipMemcpyDeviceToDevice, g_stream));
         t->key_rows = std::move(nk);
+        if (plan.n_keys) {
+            DevBuf nn;
+            nn.alloc((size_t)nc);
+            CHKV(hipMemcpyAsync(nn.p, t->knull.p, (size_t)t->n_rows,
+                                hipMemcpyDeviceToDevice, g_stream));
+            t->knull = std::move(nn);
+        }
         for (size_t i = 0; i < t->payload.size(); i++) {
             DevBuf np;
             np.alloc((size_t)nc * 8);
@@ -5889,7 +6268,90 @@ struct BuildOp : Op {
         auto it = g_tables.find(plan.semijoin_table);
         if (it == g_tables.end())
             throw std::runtime_error("semijoin table not found");
+        reject_multikey(it->second.get(), "a semijoin_table");
         return it->second.get();
+    }
+    /* multi-key chained build: the surviving rows go through the selection
+     * path (row ids + payloads), then k_mk_gather widens their key
+     * channels into key_rows / knull.  Every check runs before anything
+     * changes, so a rejected page leaves the build as it was. */
+    void add_input_multikey(const pg_page* in)
+    {
+        check_multikey_cols("HASH_BUILD", plan.n_keys, plan.key_cols, in,
+                            t->key_tag);
+        for (int i = 0; i < plan.n_payload; i++) {
+            const int32_t c = plan.payload_col[i];
+            const std::string name = "HASH_BUILD: payload_col[" +
+                                     std::to_string(i) + "] (column " +
+                                     std::to_string(c) + ")";
+            if (c < 0 || c >= in->n_cols)
+                throw std::runtime_error(
+                    name + " is outside the page's " +
+                    std::to_string(in->n_cols) + " columns");
+            const int tag = in->cols[c].tag;
+            if (tag != PG_T_U8 && tag != PG_T_I32 && tag != PG_T_I64 &&
+                tag != PG_T_F64)
+                throw std::runtime_error(
+                    name + ": payloads of a multi-key build are U8, I32, "
+                           "I64 or F64 columns");
+            if (t->ptag[i] >= 0 && t->ptag[i] != tag)
+                throw std::runtime_error(
+                    name + ": type " + std::to_string(tag) +
+                    " differs from the first page's " +
+                    std::to_string(t->ptag[i]));
+        }
+        const Table* semi = plan.semijoin_table > 0 ? semi_table() : nullptr;
+        if (semi && plan.semijoin_col < 0)
+            throw std::runtime_error("HASH_BUILD: semijoin_col is negative");
+        StagedPage sp;
+        sp.stage(in);
+        pg_plan_filter_project fp{};
+        fp.n_preds = plan.n_preds;
+        memcpy(fp.preds, plan.preds, sizeof(fp.preds));
+        fp.n_proj = 1 + plan.n_payload;
+        fp.proj[0].kind = PG_PROJ_ROWID;
+        for (int i = 0; i < plan.n_payload; i++) {
+            fp.proj[1 + i].kind = PG_PROJ_IDENT;
+            fp.proj[1 + i].a = plan.payload_col[i];
+        }
+        int64_t chunk = sel_chunk(sp.pg.n_rows);
+        SelResult r = sel_count(sp.pg, fp, semi, plan.semijoin_col, chunk);
+        if (t->n_rows + r.n > (int64_t)INT32_MAX)
+            throw std::runtime_error(
+                "HASH_BUILD: a multi-key build holds at most 2^31-1 rows "
+                "(row ids are 32-bit)");
+        for (int k = 0; k < plan.n_keys; k++)
+            t->key_tag[k] = in->cols[plan.key_cols[k]].tag;
+        for (int i = 0; i < plan.n_payload; i++)
+            t->ptag[i] = in->cols[plan.payload_col[i]].tag;
+        grow(t->n_rows + r.n);
+        DevBuf rowid;
+        rowid.alloc((size_t)(r.n ? r.n : 1) * 8);
+        emit_outs outs{};
+        outs.n = fp.n_proj;
+        outs.ptr[0] = rowid.p;
+        outs.tag[0] = PG_T_I64;
+        for (int i = 0; i < plan.n_payload; i++) {
+            outs.ptr[1 + i] = (int8_t*)t->payload[i].p +
+                              t->n_rows * type_size(t->ptag[i]);
+            outs.tag[1 + i] = t->ptag[i];
+        }
+        sel_emit(sp.pg, fp, semi, plan.semijoin_col, chunk, r, outs);
+        if (r.n) {
+            mk_keys mk{};
+            mk.n = plan.n_keys;
+            for (int k = 0; k < plan.n_keys; k++)
+                mk.col[k] = plan.key_cols[k];
+            int64_t nb = (r.n + 255) / 256;
+            hipLaunchKernelGGL(
+                k_mk_gather, dim3((unsigned)(nb < 2048 ? nb : 2048)),
+                dim3(256), 0, g_stream, sp.pg, mk,
+                (const int64_t*)rowid.p, r.n,
+                (int64_t*)t->key_rows.p + t->n_rows * plan.n_keys,
+                (uint8_t*)t->knull.p + t->n_rows);
+            CHKV(hipStreamSynchronize(g_stream));
+        }
+        t->n_rows += r.n;
     }
     void add_input(const pg_page* in) override
     {
@@ -5899,6 +6361,10 @@ struct BuildOp : Op {
                 "the key range itself)");
         check_pred_types("HASH_BUILD", plan.preds, preds_used(plan.n_preds),
                          in);
+        if (plan.n_keys) {
+            add_input_multikey(in);
+            return;
+        }
         StagedPage sp;
         sp.stage(in);
         /* resolve payload tags on first page (payload 0 is u8 when it
@@ -6074,6 +6540,7 @@ struct BuildOp : Op {
             if (it == g_tables.end())
                 throw std::runtime_error("semijoin table not found");
             semi = it->second.get();
+            reject_multikey(semi, "a semijoin_table");
         }
         int64_t chunk = sel_chunk(sp.pg.n_rows);
         SelResult r =
@@ -6177,6 +6644,45 @@ struct BuildOp : Op {
             g_tables[tbl] = std::move(t);
             return;
         }
+        if (plan.n_keys) {
+            if (t->n_rows > (int64_t)INT32_MAX)
+                throw std::runtime_error(
+                    "HASH_BUILD: a multi-key build holds at most 2^31-1 "
+                    "rows (row ids are 32-bit)");
+            int64_t cap = next_pow2(t->n_rows * 2 + 16); /* fill <= 0.5 */
+            t->cap = cap;
+            t->mask = cap - 1;
+            t->local_mask = cap - 1;
+            t->keys.alloc((size_t)cap * 8); /* the slot words */
+            t->next.alloc((size_t)(t->n_rows ? t->n_rows : 1) * 4);
+            CHKV(hipMemsetAsync(t->keys.p, 0xff, (size_t)cap * 8, g_stream));
+            CHKV(hipMemsetAsync(t->next.p, 0xff,
+                                (size_t)(t->n_rows ? t->n_rows : 1) * 4,
+                                g_stream));
+            DevBuf err;
+            err.alloc(8);
+            err.zero();
+            if (t->n_rows) {
+                int64_t nb = (t->n_rows + 255) / 256;
+                hipLaunchKernelGGL(
+                    k_mk_insert, dim3((unsigned)(nb < 2048 ? nb : 2048)),
+                    dim3(256), 0, g_stream, (const int64_t*)t->key_rows.p,
+                    (const uint8_t*)t->knull.p, t->n_rows, plan.n_keys,
+                    (unsigned long long*)t->keys.p, (int32_t*)t->next.p,
+                    t->mask, (unsigned long long*)err.p);
+            }
+            unsigned long long e = 0;
+            CHKV(hipMemcpyAsync(&e, err.p, 8, hipMemcpyDeviceToHost,
+                                g_stream));
+            CHKV(hipStreamSynchronize(g_stream));
+            if (e)
+                throw std::runtime_error(
+                    "HASH_BUILD: multi-key insert found no free slot");
+            std::lock_guard<std::mutex> lk(g_mu);
+            tbl = g_next_table++;
+            g_tables[tbl] = std::move(t);
+            return;
+        }
         int64_t cap = next_pow2(t->n_rows * 2 + 16); /* fill <= 0.5 */
         t->cap = cap;
         t->mask = cap - 1;
@@ -6252,6 +6758,8 @@ struct JoinOp : Op {
     DevBuf marks;
     std::vector<int32_t> probe_tags; /* emitted probe columns as typed in
                                         the first page fed (drain page) */
+    int32_t key_tag[4] = {-1, -1, -1, -1}; /* multi-key: the key channels
+                                              as typed in the first page */
     bool probe_outer() const
     {
         return plan.mode == PG_JOIN_PROBE_OUTER ||
@@ -6290,6 +6798,33 @@ struct JoinOp : Op {
                 "cannot probe a key-set-only table");
         if (plan.mode < 0 || plan.mode > PG_JOIN_FULL_OUTER)
             throw std::runtime_error("unknown LOOKUP_JOIN mode");
+        if (plan.n_keys < 0 || plan.n_keys > 4)
+            throw std::runtime_error(
+                "LOOKUP_JOIN: n_keys must be 0..4, got " +
+                std::to_string(plan.n_keys));
+        if (plan.n_keys != t->n_keys)
+            throw std::runtime_error(
+                "LOOKUP_JOIN: the plan has n_keys = " +
+                std::to_string(plan.n_keys) + " but the table was built "
+                "with n_keys = " + std::to_string(t->n_keys) +
+                (plan.n_keys && t->n_keys
+                     ? ""
+                     : " (0 is the legacy single key_col)"));
+        if (plan.n_keys) {
+            if (!emit_mode())
+                throw std::runtime_error(
+                    "LOOKUP_JOIN mode " + std::to_string(plan.mode) +
+                    " cannot probe a multi-key (n_keys >= 1) table: modes "
+                    "0, 4, 5 and 6 only");
+            for (int k = 0; k < plan.n_keys; k++)
+                if (plan.key_cols[k] < 0)
+                    throw std::runtime_error(
+                        "LOOKUP_JOIN: n_keys = " +
+                        std::to_string(plan.n_keys) + " but key_cols[" +
+                        std::to_string(k) + "] is negative");
+            if (plan.n_emit < 0 || plan.n_emit > 8)
+                throw std::runtime_error("n_emit must be 0..8");
+        }
         if (outer() && (plan.n_emit < 0 || plan.n_emit > 8))
             throw std::runtime_error("n_emit must be 0..8");
         if (outer() && t->range_group)
@@ -6298,7 +6833,7 @@ struct JoinOp : Op {
         if (marking()) {
             /* the drain walks build-row arrays, which only chained tables
              * keep (slot-payload and dense tables have no row order) */
-            if (t->slot_payloads || t->dense || !t->head.p)
+            if (t->slot_payloads || t->dense || (!t->head.p && !t->n_keys))
                 throw std::runtime_error(
                     plan.mode == PG_JOIN_LOOKUP_OUTER
                         ? "LOOKUP_JOIN mode 5 (PG_JOIN_LOOKUP_OUTER) needs "
@@ -6443,6 +6978,7 @@ struct JoinOp : Op {
                 throw std::runtime_error(
                     "mode 3 needs an agg/keyed table2 for the groups");
             t2 = it2->second.get();
+            reject_multikey(t2, "table2");
             if (t2->pack_bits)
                 throw std::runtime_error(
                     "mode 3 groups table cannot be packed");
@@ -6458,6 +6994,17 @@ struct JoinOp : Op {
     void add_input(const pg_page* in) override
     {
         check_pred_types("LOOKUP_JOIN", plan.preds, used_preds(), in);
+        if (plan.n_keys) {
+            check_multikey_cols("LOOKUP_JOIN", plan.n_keys, plan.key_cols,
+                                in, key_tag);
+            for (int o = 0; o < plan.n_emit; o++)
+                if (plan.emit_probe_cols[o] < 0 ||
+                    plan.emit_probe_cols[o] >= in->n_cols)
+                    throw std::runtime_error(
+                        "LOOKUP_JOIN: emit_probe_cols[" +
+                        std::to_string(o) + "] is outside the page's " +
+                        std::to_string(in->n_cols) + " columns");
+        }
         /* the emit joins copy fixed-width probe columns only (VARBIN emit
          * is FILTER_PROJECT's two-pass gather): refuse before any launch */
         if (emit_mode())
@@ -6471,6 +7018,8 @@ struct JoinOp : Op {
                         "emit_probe_cols[" + std::to_string(o) +
                         "] is VARBIN column " + std::to_string(ec));
             }
+        for (int k = 0; k < plan.n_keys; k++)
+            key_tag[k] = in->cols[plan.key_cols[k]].tag;
         StagedPage sp;
         sp.stage(in);
         if (plan.mode == 2) {
@@ -6616,7 +7165,9 @@ struct JoinOp : Op {
         }
         /* emit mode: per-block count -> host scan -> prefix emit */
         int64_t n = sp.pg.n_rows;
-        if (outer() && probe_tags.empty())
+        /* the multi-key path types its pages like the outer modes do */
+        const bool typed_cols = outer() || plan.n_keys;
+        if (typed_cols && probe_tags.empty())
             for (int o = 0; o < plan.n_emit; o++)
                 probe_tags.push_back(
                     sp.pg.cols[plan.emit_probe_cols[o]].tag);
@@ -6626,7 +7177,7 @@ struct JoinOp : Op {
             op.pg.n_cols = plan.n_emit + (int32_t)t->payload.size();
             for (int c = 0; c < op.pg.n_cols; c++) {
                 op.pg.cols[c].tag = PG_T_I64;
-                if (outer()) /* the columns a non-empty page would have */
+                if (typed_cols) /* the columns a non-empty page would have */
                     op.pg.cols[c].tag =
                         c < plan.n_emit ? probe_tags[c]
                                         : payload_tag(t, c - plan.n_emit);
@@ -6655,12 +7206,29 @@ struct JoinOp : Op {
                        t->local_mask, t->pack_bits,                      \
                        (const unsigned long long*)t->kbits.p, t->bmax,   \
                        dv8, dv32, dcap, chunk, (int64_t*)d_counts.p)
+#define LAUNCH_MK_COUNT(PO, MK)                                          \
+    hipLaunchKernelGGL((k_mk_probe_count<PO, MK>), dim3(FLT_NB),         \
+                       dim3(256), 0, g_stream, sp.pg, plan,              \
+                       (const unsigned long long*)t->keys.p,             \
+                       (const int32_t*)t->next.p, t->mask,               \
+                       (const int64_t*)t->key_rows.p, chunk,             \
+                       (int64_t*)d_counts.p)
+        if (plan.n_keys) {
+            g_multikey_probe_pages++;
+            switch (plan.mode) {
+                case PG_JOIN_PROBE_OUTER: LAUNCH_MK_COUNT(true, false); break;
+                case PG_JOIN_LOOKUP_OUTER: LAUNCH_MK_COUNT(false, true); break;
+                case PG_JOIN_FULL_OUTER: LAUNCH_MK_COUNT(true, true); break;
+                default: LAUNCH_MK_COUNT(false, false);
+            }
+        } else
         switch (plan.mode) {
             case PG_JOIN_PROBE_OUTER: LAUNCH_PROBE_COUNT(true, false); break;
             case PG_JOIN_LOOKUP_OUTER: LAUNCH_PROBE_COUNT(false, true); break;
             case PG_JOIN_FULL_OUTER: LAUNCH_PROBE_COUNT(true, true); break;
             default: LAUNCH_PROBE_COUNT(false, false);
         }
+#undef LAUNCH_MK_COUNT
 #undef LAUNCH_PROBE_COUNT
         std::vector<int64_t> h(FLT_NB);
         CHKV(hipMemcpyAsync(h.data(), d_counts.p, FLT_NB * 8,
@@ -6715,7 +7283,7 @@ struct JoinOp : Op {
         emit_outs bouts{};
         bouts.n = bp.n;
         for (int o = 0; o < bp.n; o++) {
-            const int32_t ptag = outer() ? payload_tag(t, o) : t->ptag[o];
+            const int32_t ptag = typed_cols ? payload_tag(t, o) : t->ptag[o];
             bp.ptr[o] = t->payload[o].p;
             bp.tag[o] = ptag;
             op.dev.emplace_back();
@@ -6740,12 +7308,28 @@ struct JoinOp : Op {
                        (const unsigned long long*)t->kbits.p, t->bmax,   \
                        dv8, dv32, dcap, chunk, (const int64_t*)d_offs.p, \
                        pouts, bp, bouts, oo)
+#define LAUNCH_MK_EMIT(PO, MK)                                           \
+    hipLaunchKernelGGL((k_mk_probe_emit<PO, MK>), dim3(FLT_NB),          \
+                       dim3(256), 0, g_stream, sp.pg, plan,              \
+                       (const unsigned long long*)t->keys.p,             \
+                       (const int32_t*)t->next.p, t->mask,               \
+                       (const int64_t*)t->key_rows.p, chunk,             \
+                       (const int64_t*)d_offs.p, pouts, bp, bouts, oo)
+        if (plan.n_keys)
+            switch (plan.mode) {
+                case PG_JOIN_PROBE_OUTER: LAUNCH_MK_EMIT(true, false); break;
+                case PG_JOIN_LOOKUP_OUTER: LAUNCH_MK_EMIT(false, true); break;
+                case PG_JOIN_FULL_OUTER: LAUNCH_MK_EMIT(true, true); break;
+                default: LAUNCH_MK_EMIT(false, false);
+            }
+        else
         switch (plan.mode) {
             case PG_JOIN_PROBE_OUTER: LAUNCH_PROBE_EMIT(true, false); break;
             case PG_JOIN_LOOKUP_OUTER: LAUNCH_PROBE_EMIT(false, true); break;
             case PG_JOIN_FULL_OUTER: LAUNCH_PROBE_EMIT(true, true); break;
             default: LAUNCH_PROBE_EMIT(false, false);
         }
+#undef LAUNCH_MK_EMIT
 #undef LAUNCH_PROBE_EMIT
         hot_end();
         CHKV(hipStreamSynchronize(g_stream));

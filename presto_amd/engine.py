@@ -96,7 +96,8 @@ class PlanHashBuild(C.Structure):
                 ("agg_table", C.c_int32), ("pack_bits", C.c_int32),
                 ("fill_x10", C.c_int32), ("bitmap_max_key", C.c_int64),
                 ("range_group", C.c_int32),
-                ("dense_payload_bias", C.c_int32)]
+                ("dense_payload_bias", C.c_int32),
+                ("n_keys", C.c_int32), ("key_cols", C.c_int32 * 4)]
 
 
 class PlanLookupJoin(C.Structure):
@@ -113,7 +114,8 @@ class PlanLookupJoin(C.Structure):
                 ("acc_pack", C.c_int32), ("acc_pack_shift", C.c_int32 * 6),
                 ("acc_pack_width", C.c_int32 * 6),
                 ("acc_pack_cnt_shift", C.c_int32),
-                ("acc_pack_cnt_width", C.c_int32)]
+                ("acc_pack_cnt_width", C.c_int32),
+                ("n_keys", C.c_int32), ("key_cols", C.c_int32 * 4)]
 
 
 class PlanGroupBy(C.Structure):
@@ -160,6 +162,14 @@ class PlanMarkDistinct(C.Structure):
                 ("emit_cols", C.c_int32 * 16)]
 
 
+# pg_abi_struct_sizes order, and the plans pg_abi_plan_size alone reports
+_ABI_STRUCTS = (PgCol, PgPage, Pred, Proj, Agg, PlanFilterProject,
+                PlanHashAggSmall, PlanHashBuild, PlanLookupJoin, PlanGroupBy,
+                PlanTopN, PlanPartition)
+_ABI_PLANS = ((PlanOrderBy, OP_ORDER_BY), (PlanWindow, OP_WINDOW),
+              (PlanMarkDistinct, OP_MARK_DISTINCT))
+
+
 class _Lib:
     def __init__(self):
         if not _SO.exists():
@@ -190,6 +200,35 @@ class _Lib:
         self.c.pg_abi_plan_size.restype = C.c_int32
         self.c.pg_sortkey_u64.argtypes = [C.c_int32, C.c_int32, C.c_uint64]
         self.c.pg_sortkey_u64.restype = C.c_uint64
+        self.c.pg_multikey_probe_pages.argtypes = []
+        self.c.pg_multikey_probe_pages.restype = C.c_int64
+        self.c.pg_abi_struct_sizes.argtypes = [C.POINTER(C.c_int32),
+                                               C.c_int32]
+        self.c.pg_abi_struct_sizes.restype = C.c_int32
+        self._check_struct_sizes()
+
+    def _check_struct_sizes(self):
+        """The load-time guard the header promises: every mirrored struct
+        must be as large as the library compiled it."""
+        n = self.c.pg_abi_struct_sizes(None, 0)
+        sizes = (C.c_int32 * n)()
+        self.c.pg_abi_struct_sizes(sizes, n)
+        bad = [f"{cls.__name__}: ctypes {C.sizeof(cls)}, library {sz}"
+               for cls, sz in zip(_ABI_STRUCTS, sizes)
+               if C.sizeof(cls) != sz]
+        for cls, kind in _ABI_PLANS:
+            sz = self.c.pg_abi_plan_size(kind)
+            if C.sizeof(cls) != sz:
+                bad.append(f"{cls.__name__}: ctypes {C.sizeof(cls)}, "
+                           f"library {sz}")
+        if n < len(_ABI_STRUCTS):
+            bad.append(f"pg_abi_struct_sizes reports {n} structs, the "
+                       f"binding mirrors {len(_ABI_STRUCTS)}")
+        if bad:
+            raise RuntimeError(
+                f"{_SO} does not match the ctypes mirrors of "
+                "include/presto_gpu.h (rebuild the library): "
+                + "; ".join(bad))
 
     def err(self):
         return (self.c.pg_last_error() or b"").decode()

@@ -873,6 +873,68 @@ def q9(part: Page, supp: Page, orders: Page, ps: Page, li: Page):
         return profit
 
 
+def q9_multikey(part: Page, supp: Page, orders: Page, ps: Page, li: Page):
+    """q9 with the partsupp lookup as ONE two-key emit join on (partkey,
+    suppkey): a multi-key chained build of partsupp and a probe that emits
+    the one matching row, instead of q9's four candidates per lineitem and
+    the suppkey equality FILTER_PROJECT behind them.  Everything else, and
+    the return value, is q9's."""
+    with Scope() as s:
+        og = s.build(pl.flag_set(
+            part.channel("partkey"), part.n_rows,
+            preds=[pl.pred_varbin(part.channel("name"), CMP_CONTAINS,
+                                  b"green")]), part)
+        f, gli = s.pipe(OP_FILTER_PROJECT, pl.filter_project(
+            [pl.ident(li.channel(n)) for n in
+             ("partkey", "suppkey", "orderkey", "quantity", "extendedprice",
+              "discount")],
+            semijoin_table=og.table(),
+            semijoin_col=li.channel("partkey")), li)
+        # gli: [pk, sk, ok, qty, ep, dc]
+
+        ops_ = s.build(pl.hash_build(
+            [ps.channel("partkey"), ps.channel("suppkey")],
+            payload=[ps.channel("supplycost")],
+            capacity_hint=ps.n_rows), ps)
+        ja, pb = s.pipe(OP_LOOKUP_JOIN,
+                        pl.emit_join(ops_.table(), [0, 1], [1, 2, 3, 4, 5]),
+                        gli)
+        # pb: [sk, ok, qty, ep, dc, cost]
+
+        os_ = s.build(pl.hash_build(
+            supp.channel("suppkey"), payload=[supp.channel("nationkey")],
+            capacity_hint=supp.n_rows), supp)
+        jb, pc = s.pipe(OP_LOOKUP_JOIN,
+                        pl.emit_join(os_.table(), 0, [1, 2, 3, 4, 5]), pb)
+        # pc: [ok, qty, ep, dc, cost, nat]
+
+        oo = s.build(pl.hash_build(
+            orders.channel("orderkey"),
+            payload=[orders.channel("orderdate")],
+            capacity_hint=okey_max(orders.n_rows), dense_array=1), orders)
+        jc, pd = s.pipe(OP_LOOKUP_JOIN,
+                        pl.emit_join(oo.table(), 0, [1, 2, 3, 4, 5]), pc)
+        # pd: [qty, ep, dc, cost, nat, odate]
+
+        gop = s.run(OP_GROUPBY_MULTI, pl.group_by(
+            [4, 5],  # nat, odate
+            [pl.sum_dec(pl.disc_price(1, 2), 4),
+             pl.sum_dec(pl.mul(3, 0), 4)],
+            25 * 2500 + 1024), pd)
+        gout = gop.get_output(["nat", "odate", "rev", "cost", "cnt"])
+        s.release(gop)
+        profit = [[0] * 7 for _ in range(25)]
+        years = np.searchsorted(np.asarray(Q9_YEAR_BOUNDS[1:]),
+                                np.asarray(gout["odate"]), side="right")
+        for i in range(len(gout["nat"])):
+            y = int(years[i])
+            if y < 7:
+                profit[int(gout["nat"][i])][y] += \
+                    int(gout["rev"][i]) - int(gout["cost"][i])
+        s.release(jc, jb, ja, f, og, ops_, os_, oo)
+        return profit
+
+
 def q13(n_cust: int, orders, max_count=64):
     """Q13 customer distribution (q13.sql): the NOT LIKE
     '%special%requests%' comment filter runs as the ordered

@@ -10,6 +10,8 @@ unknown name is a TypeError.
 """
 import ctypes as C
 
+import numbers
+
 from .engine import (
     Pred, Proj, Agg, PlanFilterProject, PlanHashAggSmall, PlanHashBuild,
     PlanLookupJoin, PlanGroupBy, PlanTopN, PlanPartition, PlanOrderBy,
@@ -179,12 +181,29 @@ def _aggs(plan, preds, filters, aggs):
           [-1 if f is None else len(preds) + f for _, f in pairs])
 
 
+def _join_keys(plan, key_col):
+    """key_col of a build or a join: an int is the single bigint key
+    (n_keys = 0, the path every plan took before multi-key joins); a
+    sequence of 1..4 channels, most significant first, is a multi-key
+    join key (n_keys = len, key_cols)."""
+    if isinstance(key_col, numbers.Integral):
+        plan.key_col = int(key_col)
+        return
+    keys = list(key_col)
+    if not keys:
+        raise ValueError("key_cols: a multi-key join needs at least one "
+                         "key (pass an int for the single-key path)")
+    plan.n_keys = _fill(plan.key_cols, "key_cols", keys)
+
+
 # ---- one constructor per operator kind ----
 def hash_build(key_col=0, *, preds=(), payload=(), semijoin_table=-1,
                **fields):
+    """key_col: an int, or a sequence of 1..4 channels for a multi-key
+    chained build (see _join_keys)."""
     p = PlanHashBuild()
     p.n_preds = _fill(p.preds, "preds", preds)
-    p.key_col = key_col
+    _join_keys(p, key_col)
     p.n_payload = _fill(p.payload_col, "payload_col", payload)
     p.semijoin_table = semijoin_table
     return _set(p, fields)
@@ -207,10 +226,12 @@ def lookup_join(table, key_col, mode, *, preds=(), filters=(), emit=(),
     """mode 0 emits `emit` probe channels + the payloads (modes 4-6 are
     its outer variants: left_join / right_join / full_join); mode 1 is the
     fused grouped aggregate (single proj=/dec_scale=, or aggs= with
-    optional filters= and acc_pack fields); modes 2/3 take table2= etc."""
+    optional filters= and acc_pack fields); modes 2/3 take table2= etc.
+    key_col: an int, or a sequence of 1..4 channels to probe a multi-key
+    table (emit modes only)."""
     p = PlanLookupJoin()
     p.table = table
-    p.key_col = key_col
+    _join_keys(p, key_col)
     p.mode = mode
     _aggs(p, preds, filters, aggs)
     p.n_emit = _fill(p.emit_probe_cols, "emit_probe_cols", emit)
