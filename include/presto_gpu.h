@@ -71,6 +71,11 @@ int64_t pg_q1_fast_launches(void);
  * packed Q3/Q5 orders-build shape; PG_BUILD_STAGED=0 in the environment
  * at build creation forces the generic kernel) */
 int64_t pg_build_staged_launches(void);
+/* how many LOOKUP_JOIN mode-2 pages this process has sent to the Q5-shape
+ * kernel (k_probe_agg_q5) rather than the generic k_probe_agg_fused2: the
+ * gate is per page (packed table, no preds, DISC_PRICE over F64 columns,
+ * I64 keys, dec_scale 4, 16-byte aligned key columns, no null masks) */
+int64_t pg_mode2_q5_launches(void);
 /* how many grouped (mode 1, single aggregate) LOOKUP_JOIN finishes this
  * process has extracted from the table's hit list (a gather of the slots
  * the probes first touched) rather than by scanning the accumulator array

@@ -166,6 +166,8 @@ extern "C" int64_t pg_build_staged_launches(void)
 {
     return g_build_staged_launches;
 }
+static int64_t g_mode2_q5_launches = 0;
+extern "C" int64_t pg_mode2_q5_launches(void) { return g_mode2_q5_launches; }
 static int64_t g_groups_list_extractions = 0;
 extern "C" int64_t pg_groups_list_extractions(void)
 {
@@ -473,6 +475,20 @@ __device__ inline int64_t d_bfly_i64(int64_t v)
 {
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_xor(v, s, WAVE);
+    return v;
+}
+/* the same butterfly for exact tick sums (Math.addExact semantics).  A lane
+ * performs only six of the tree's 63 adds; the other partial sums form in
+ * partner lanes and would arrive already wrapped, so every lane checks its
+ * own adds and the wave votes: the result is true in all 64 lanes when any
+ * add anywhere in the tree left int64.  All lanes of the wave must call. */
+__device__ inline int64_t d_bfly_i64_ck(int64_t v, bool* wrapped)
+{
+    bool w = false;
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1)
+        w |= __builtin_add_overflow(v, __shfl_xor(v, s, WAVE), &v);
+    *wrapped = __any(w);
     return v;
 }
 
@@ -3018,15 +3034,18 @@ __global__ __launch_bounds__(256) void k_probe_agg_fused2(
             flo[g] = nlo;
         }
     }
-    /* wave reduce ticks/count (exact), then one atomic per wave; the
-     * fx128 halves go through carry-aware atomics per lane (exact,
-     * order-independent) */
+    /* wave reduce ticks/count (exact; a wave total that leaves int64 bumps
+     * the overflow slot like the per-thread add and the atomic do), then
+     * one atomic per wave; the fx128 halves go through carry-aware atomics
+     * per lane (exact, order-independent) */
 #pragma unroll
     for (int g = 0; g < MAXG; g++) {
-        int64_t a = d_bfly_i64(acc[g]);
+        bool wrapped;
+        int64_t a = d_bfly_i64_ck(acc[g], &wrapped);
         int64_t c = d_bfly_i64((int64_t)cnt[g]);
         if ((threadIdx.x & 63) == 0) {
-            if (a) d_atomic_add_dec_ck(&out_dec[g], a, out_cnt + MAXG);
+            if (wrapped) atomicAdd(out_cnt + MAXG, 1ull); /* ovf slot */
+            else if (a) d_atomic_add_dec_ck(&out_dec[g], a, out_cnt + MAXG);
             if (c) atomicAdd(&out_cnt[g], (unsigned long long)c);
         }
         if (flo[g] | fhi[g]) {
@@ -3141,10 +3160,12 @@ __global__ __launch_bounds__(256) void k_probe_agg_q5(
     }
 #pragma unroll
     for (int g = 0; g < MAXG; g++) {
-        int64_t a = d_bfly_i64(acc[g]);
+        bool wrapped;
+        int64_t a = d_bfly_i64_ck(acc[g], &wrapped);
         int64_t c = d_bfly_i64((int64_t)cnt[g]);
         if ((threadIdx.x & 63) == 0) {
-            if (a) d_atomic_add_dec_ck(&out_dec[g], a, out_cnt + MAXG);
+            if (wrapped) atomicAdd(out_cnt + MAXG, 1ull); /* ovf slot */
+            else if (a) d_atomic_add_dec_ck(&out_dec[g], a, out_cnt + MAXG);
             if (c) atomicAdd(&out_cnt[g], (unsigned long long)c);
         }
         if (flo[g] | fhi[g]) {
@@ -7053,6 +7074,7 @@ struct JoinOp : Op {
                     t->pack_bits, (const unsigned long long*)t->kbits.p, t->bmax,
                     (const uint8_t*)t2->payload[0].p,
                     t2->cap, a, a + 8, a + 16, a + 24);
+                g_mode2_q5_launches++;
             } else {
                 hipLaunchKernelGGL(k_probe_agg_fused2<8>, dim3(4096),
                                    dim3(256), 0, g_stream, sp.pg, plan,
