@@ -605,7 +605,31 @@ typedef struct {
      * count; agg_filter[a] >= 0 indexes a predicate in preds[] that
      * gates aggregate a alone (row-level filtering still uses
      * preds[0..n_preds)).  Overflow-checked (Math.addExact).  Output
-     * page after finish: key, payloads..., agg0..agg{n-1}, count. */
+     * page after finish: key, payloads..., agg0..agg{n-1}, count, one row
+     * per key with count >= 1, in no particular order.
+     *   - Functions: PG_AGG_COUNT (its proj is ignored), PG_AGG_SUM_DEC
+     *     and PG_AGG_SUM_I64 only — every accumulator is an int64 tick
+     *     sum.  SUM_F64, MIN and MAX fail pg_op_create with an error that
+     *     names the aggregate and the function.
+     *   - The count is the number of rows that passed preds[0..n_preds)
+     *     and found their key.  A FILTER gates its own aggregate and
+     *     nothing else: a row it rejects adds nothing to that sum, still
+     *     feeds every other aggregate and still counts, so a group whose
+     *     rows a FILTER rejects all the same comes out with sum 0 and its
+     *     full count.  agg_filter[a] may also name a row predicate (an
+     *     index below n_preds).
+     *   - A row that fails the row predicates is skipped before its key
+     *     is read.
+     *   - Overflow: a group whose exact total leaves int64 raises at
+     *     finish when its addends share one sign.  With mixed signs
+     *     detection follows the order of the partial sums: totals whose
+     *     sum of |addends| stays below 2^63 never raise.
+     *   - Several pages, and several operators one after the other on one
+     *     table, accumulate into the same slots; the table keeps the
+     *     layout of its first multi-agg operator (n_aggs and the acc_pack
+     *     fields below) and a later operator that declares another one
+     *     fails pg_op_create with "different multi-agg layout".
+     *     pg_table_reset_acc zeroes the sums and keeps the layout. */
     int32_t n_aggs; /* 0 = legacy single proj; 1..6 multi */
     pg_agg aggs[6];
     int32_t agg_filter[6];
@@ -625,7 +649,21 @@ typedef struct {
      * width and raises the overflow error on violation (gross width
      * mistakes fail loudly; the bound itself is the caller's integrity
      * fact, as with pack_bits).  Output schema is unchanged — group
-     * extraction unpacks the fields. */
+     * extraction unpacks the fields.
+     *   - Field widths and the count width are 1..63, shifts are >= 0
+     *     (-1 = own word, for an aggregate only) and shift + width <= 64;
+     *     fields may not overlap each other or the count.  A 64-bit field
+     *     is an own word.  Anything else fails pg_op_create with an error
+     *     naming the field; the width of an own-word aggregate is not
+     *     read.
+     *   - A bit field is unsigned.  A non-negative contribution that the
+     *     group's total fits never raises, up to a total of exactly
+     *     2^width - 1 (and 2^cnt_width - 1 rows), without touching the
+     *     neighbouring fields or slots.  A contribution of 2^width or
+     *     more, and a negative contribution that its run of equal keys
+     *     does not cancel, raise the overflow error at finish.
+     *   - Own words are signed int64 sums with the unpacked overflow
+     *     rules. */
     int32_t acc_pack;
     int32_t acc_pack_shift[6];
     int32_t acc_pack_width[6];
@@ -1021,7 +1059,9 @@ pg_status pg_table_destroy(int64_t table);
 /* zero an agg table's accumulators so the table (keys + chains) can be
  * reused by another fused-agg probe — the analog of reusing a lookup
  * source across probe factories (HashBuilderOperator.java:534
- * lendPartitionLookupSource is multi-consumer) */
+ * lendPartitionLookupSource is multi-consumer).  The multi-agg accumulators
+ * are zeroed too and keep their layout: the next multi-agg operator on the
+ * table must still declare the layout of the first. */
 pg_status pg_table_reset_acc(int64_t table);
 
 /* ---- SerializedPage wire interop ----

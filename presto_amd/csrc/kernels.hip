@@ -3251,11 +3251,12 @@ __global__ __launch_bounds__(256) void k_probe_agg_multi(
             if (cur_slot == -2 || key != cur_key) {
                 flush();
                 cur_key = key;
-                if (!keys) /* range-group: acc index = key-1 */
-                    cur_slot = (uint64_t)(key - 1) <= (uint64_t)mask
-                                   ? key - 1
-                                   : -1;
-                else
+                if (!keys) { /* range-group: acc index = key-1, taken
+                                unsigned so that INT64_MIN is a miss and
+                                not a signed overflow */
+                    const uint64_t s = (uint64_t)key - 1;
+                    cur_slot = s <= (uint64_t)mask ? (int64_t)s : -1;
+                } else
                     cur_slot = kbits && !d_kbit_test(kbits, bmax, key)
                                    ? -1
                                    : d_tbl_find_tagged(keys, tags, mask,
@@ -5312,7 +5313,14 @@ struct Table {
                          (n_acc+1 unpacked; fewer when acc_pack) */
     int32_t n_acc = 0;
     int32_t acc_stride = 0;
-    DevBuf kbits;     /* key-presence bitmap (dynamic-filter analog) */
+    /* the layout acc_multi was allocated for, as the first multi-agg
+     * operator declared it (unused entries zero).  A later operator must
+     * declare the same one; pg_table_reset_acc keeps it. */
+    int32_t acc_packed = 0;
+    int32_t acc_shift[6] = {0, 0, 0, 0, 0, 0};
+    int32_t acc_width[6] = {0, 0, 0, 0, 0, 0};
+    int32_t acc_cnt_shift = 0, acc_cnt_width = 0;
+    DevBuf kbits;    /* key-presence bitmap (dynamic-filter analog) */
     int64_t bmax = 0; /* bitmap covers keys [1, bmax]; 0 = none */
     bool range_group = false; /* dense-range group domain [1, cap]:
                                  keys.p stays null, acc index = key-1 */
@@ -6892,42 +6900,101 @@ struct JoinOp : Op {
                 if (plan.agg_filter[a] >= plan.n_preds &&
                     plan.agg_filter[a] >= PG_MAX_PRED)
                     throw std::runtime_error("agg_filter out of range");
+            /* the kernel knows COUNT and int64 tick sums; anything else
+             * would come back as a sum of ticks */
+            for (int a = 0; a < plan.n_aggs; a++) {
+                const int32_t fn = plan.aggs[a].func;
+                if (fn != PG_AGG_COUNT && fn != PG_AGG_SUM_DEC &&
+                    fn != PG_AGG_SUM_I64)
+                    throw std::runtime_error(
+                        "LOOKUP_JOIN: aggs[" + std::to_string(a) +
+                        "].func = " + std::to_string(fn) +
+                        (fn == PG_AGG_SUM_F64 ? " (SUM_F64)"
+                         : fn == PG_AGG_MIN   ? " (MIN)"
+                         : fn == PG_AGG_MAX   ? " (MAX)"
+                                              : "") +
+                        " is not a multi-agg function: COUNT, SUM_DEC and "
+                        "SUM_I64 only");
+            }
             int32_t want_stride = plan.n_aggs + 1;
+            int32_t lay_shift[6] = {0, 0, 0, 0, 0, 0};
+            int32_t lay_width[6] = {0, 0, 0, 0, 0, 0};
+            int32_t lay_cnt_shift = 0, lay_cnt_width = 0;
             if (plan.acc_pack) {
                 want_stride = 1;
+                /* widths and shifts are validated before any shift by
+                 * them: a 64-bit shift is undefined on the host and on
+                 * the device */
+                lay_cnt_shift = plan.acc_pack_cnt_shift;
+                lay_cnt_width = plan.acc_pack_cnt_width;
+                if (lay_cnt_width < 1 || lay_cnt_width > 63)
+                    throw std::runtime_error(
+                        "acc_pack_cnt_width must be 1..63, got " +
+                        std::to_string(lay_cnt_width));
+                if (lay_cnt_shift < 0 || lay_cnt_shift + lay_cnt_width > 64)
+                    throw std::runtime_error(
+                        "acc_pack_cnt_shift must be >= 0 with shift + "
+                        "width <= 64, got shift " +
+                        std::to_string(lay_cnt_shift) + " width " +
+                        std::to_string(lay_cnt_width));
                 unsigned long long used =
-                    ((1ull << plan.acc_pack_cnt_width) - 1)
-                    << plan.acc_pack_cnt_shift;
-                if (plan.acc_pack_cnt_width < 1 ||
-                    plan.acc_pack_cnt_shift +
-                        plan.acc_pack_cnt_width > 64)
-                    throw std::runtime_error("acc_pack: bad cnt field");
+                    ((1ull << lay_cnt_width) - 1) << lay_cnt_shift;
                 for (int a = 0; a < plan.n_aggs; a++) {
-                    if (plan.acc_pack_shift[a] < 0) {
+                    const int32_t sh = plan.acc_pack_shift[a];
+                    const int32_t wd = plan.acc_pack_width[a];
+                    const std::string ix = "[" + std::to_string(a) + "]";
+                    if (sh == -1) { /* own word: the width is not read */
+                        lay_shift[a] = -1;
                         want_stride++;
                         continue;
                     }
-                    if (plan.acc_pack_width[a] < 1 ||
-                        plan.acc_pack_shift[a] +
-                            plan.acc_pack_width[a] > 64)
+                    if (wd < 1 || wd > 63)
                         throw std::runtime_error(
-                            "acc_pack: bad field bounds");
-                    unsigned long long fm =
-                        ((1ull << plan.acc_pack_width[a]) - 1)
-                        << plan.acc_pack_shift[a];
+                            "acc_pack_width" + ix + " must be 1..63 (a "
+                            "64-bit field is an own word, shift -1), got " +
+                            std::to_string(wd));
+                    if (sh < 0 || sh + wd > 64)
+                        throw std::runtime_error(
+                            "acc_pack_shift" + ix + " must be -1 (own "
+                            "word) or >= 0 with shift + width <= 64, got "
+                            "shift " + std::to_string(sh) + " width " +
+                            std::to_string(wd));
+                    unsigned long long fm = ((1ull << wd) - 1) << sh;
                     if (used & fm)
                         throw std::runtime_error(
-                            "acc_pack: overlapping fields");
+                            "acc_pack_shift" + ix + ": the field overlaps "
+                            "the count field or an earlier field");
                     used |= fm;
+                    lay_shift[a] = sh;
+                    lay_width[a] = wd;
                 }
             }
-            if (t->acc_multi.p && (t->n_acc != plan.n_aggs ||
-                                   t->acc_stride != want_stride))
-                throw std::runtime_error(
-                    "table already carries a different multi-agg layout");
+            if (t->acc_multi.p) {
+                bool same = t->n_acc == plan.n_aggs &&
+                            t->acc_stride == want_stride &&
+                            t->acc_packed == (plan.acc_pack ? 1 : 0) &&
+                            t->acc_cnt_shift == lay_cnt_shift &&
+                            t->acc_cnt_width == lay_cnt_width;
+                for (int a = 0; a < 6; a++)
+                    same = same && t->acc_shift[a] == lay_shift[a] &&
+                           t->acc_width[a] == lay_width[a];
+                if (!same)
+                    throw std::runtime_error(
+                        "table already carries a different multi-agg "
+                        "layout (n_aggs, acc_pack, acc_pack_shift/width "
+                        "and the count field must all match the first "
+                        "multi-agg operator's)");
+            }
             if (!t->acc_multi.p) {
                 t->n_acc = plan.n_aggs;
                 t->acc_stride = want_stride;
+                t->acc_packed = plan.acc_pack ? 1 : 0;
+                for (int a = 0; a < 6; a++) {
+                    t->acc_shift[a] = lay_shift[a];
+                    t->acc_width[a] = lay_width[a];
+                }
+                t->acc_cnt_shift = lay_cnt_shift;
+                t->acc_cnt_width = lay_cnt_width;
                 t->acc_multi.alloc((size_t)t->cap * want_stride * 8);
                 t->acc_multi.zero();
                 CHKV(hipStreamSynchronize(g_stream));
