@@ -1063,6 +1063,11 @@ pg_status pg_table_destroy(int64_t table);
  * are zeroed too and keep their layout: the next multi-agg operator on the
  * table must still declare the layout of the first. */
 pg_status pg_table_reset_acc(int64_t table);
+/* bytes of the table's byte-tag array (one tag per slot), 0 when the table
+ * carries none: hash tables below 2^26 slots, and non-partitioned
+ * agg_table builds with a key bitmap, whose bitmap already is an exact
+ * membership test (tests pin which tables carry tags) */
+int64_t pg_table_tag_bytes(int64_t table);
 
 /* ---- SerializedPage wire interop ----
  * Presto's exchange wire format, restated from

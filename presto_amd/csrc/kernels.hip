@@ -1515,19 +1515,44 @@ __global__ __launch_bounds__(256) void k_tbl_insert_direct(
  * consecutive rows of a 1024-row block tile and every load of a stage is
  * issued for all of them before any result is consumed:
  *   A  nontemporal vector loads of the predicate / semijoin / lookup /
- *      build-key columns, unconditionally;
- *   B  predicates, then the dense flag and lookup gathers of the rows
- *      that pass, issued together;
+ *      build-key columns and the loads of a payload column of its own,
+ *      unconditionally;
+ *   B  predicates, then the dense flag and lookup gathers of all rows,
+ *      from an index clamped to 0 for the rows that did not pass, and the
+ *      select afterwards;
  *   C  pack and bitmap range checks, bitmap set, bounded CAS probe, tag
  *      store — per row exactly what the generic kernel does; the first
  *      CAS of every surviving row goes out before any result is read.
+ * A load that sits behind a branch of its own is waited for before the
+ * next one is issued, even where the condition is the same for the whole
+ * launch, so the shape of the page (number of predicates, semijoin,
+ * lookup, payload source) is a template parameter and the host picks the
+ * instance (bs_pick); only the last, partial tile of a page takes the
+ * scalar path with its per-row bounds tests.
  * Measured on the SF100 Q3 build (profiles/build_staged.json): 2.80 ms ->
  * 2.04 ms.  Deferring the build-key load to the ~10% of rows that pass
  * (2.08 ms) and compacting a tile's survivors through LDS so that the CAS
  * chains run in full waves (2.13 ms) both measured slower and are not
- * kept.  No block waits on another; every loop is bounded. */
+ * kept.  Issuing each stage's loads together took 78 VGPRs to 53 and the
+ * occupancy from 6 to 8 waves per SIMD, but only 2.04 -> 2.00 ms
+ * (profiles/q3_streams.json): the kernel is not bound by those round
+ * trips.  Loading the next tile's stage A between the gathers and their
+ * first use (74 VGPRs, occupancy 6; 1.74 against 1.76 ms) and grids of
+ * 2048 and 8192 blocks (1.77, 1.72 ms) are inside the run-to-run spread
+ * and are not kept.  What did pay is leaving the tag array out under an
+ * exact bitmap (BuildOp::init): 2.00 -> 1.76 ms.
+ * No block waits on another; every loop is bounded. */
 #define BS_R 4
 #define BS_TILE (256 * BS_R)
+#define BS_GRID 4096 /* blocks at most; a block walks tiles BS_GRID apart */
+/* payload source of a staged page */
+enum {
+    BS_PAY_PRED = 0, /* the predicate column #pay_pred */
+    BS_PAY_LOOKUP,   /* the dense u8 lookup */
+    BS_PAY_I32,      /* a column of its own, by type */
+    BS_PAY_U8,
+    BS_PAY_I64
+};
 struct staged_args {
     const int32_t* pc[2]; /* predicate columns (I32) */
     int64_t pval[2];
@@ -1556,36 +1581,32 @@ __device__ inline bool d_cmp_i64(int32_t op, int64_t v, int64_t x)
         default: return v != x;
     }
 }
-__device__ inline void d_bs_load_i32(const int32_t* p, int64_t base,
-                                     int64_t n, bool full, int64_t* out)
+/* BS_R rows of a full tile: 16-byte nontemporal loads */
+__device__ inline void d_bs_vload_i32(const int32_t* p, int32_t* out)
 {
     typedef int vi4 __attribute__((ext_vector_type(4)));
-    if (full) {
-        vi4 v = __builtin_nontemporal_load((const vi4*)(p + base));
+    vi4 v = __builtin_nontemporal_load((const vi4*)p);
 #pragma unroll
-        for (int j = 0; j < BS_R; j++) out[j] = v[j];
-    } else {
-#pragma unroll
-        for (int j = 0; j < BS_R; j++)
-            out[j] = base + j < n ? p[base + j] : 0;
-    }
+    for (int j = 0; j < BS_R; j++) out[j] = v[j];
 }
-__device__ inline void d_bs_load_i64(const int64_t* p, int64_t base,
-                                     int64_t n, bool full, int64_t* out)
+__device__ inline void d_bs_vload_i64(const int64_t* p, int64_t* out)
 {
     typedef long vl2 __attribute__((ext_vector_type(2)));
-    if (full) {
 #pragma unroll
-        for (int j = 0; j < BS_R; j += 2) {
-            vl2 v = __builtin_nontemporal_load((const vl2*)(p + base + j));
-            out[j] = v[0];
-            out[j + 1] = v[1];
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < BS_R; j++)
-            out[j] = base + j < n ? p[base + j] : 0;
+    for (int j = 0; j < BS_R; j += 2) {
+        vl2 v = __builtin_nontemporal_load((const vl2*)(p + j));
+        out[j] = v[0];
+        out[j + 1] = v[1];
     }
+}
+/* row i of a payload column of its own (the gate asks no alignment of
+ * it, so it is read by element) */
+template <int PAY>
+__device__ inline int64_t d_bs_pay(const void* p, int64_t i)
+{
+    if constexpr (PAY == BS_PAY_I32) return ((const int32_t*)p)[i];
+    else if constexpr (PAY == BS_PAY_U8) return ((const uint8_t*)p)[i];
+    else return ((const int64_t*)p)[i];
 }
 /* the probe loop of k_tbl_insert_direct for a packed word, entered with
  * the result of the first CAS already in hand */
@@ -1613,62 +1634,74 @@ __device__ inline void d_bs_probe(int64_t* keys, uint8_t* tags,
                         (unsigned long long)word);
     }
 }
+template <int NP, bool SK, bool LK, int PAY>
 __global__ __launch_bounds__(256) void k_tbl_insert_staged(
     staged_args a, int32_t pbits, int64_t* keys, uint8_t* tags,
     int64_t mask, unsigned long long* inserted,
     unsigned long long* overflow, unsigned long long* pack_err,
     unsigned long long* kbits, int64_t bmax, unsigned long long* bm_err)
 {
+    constexpr bool OWN_PAY = PAY >= BS_PAY_I32;
     const int64_t n = a.n;
     const int64_t n_tiles = (n + BS_TILE - 1) / BS_TILE;
     int64_t my_inserted = 0, my_overflow = 0, my_packerr = 0;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t base = tile * BS_TILE + (int64_t)threadIdx.x * BS_R;
-        const bool full = base + BS_R <= n; /* else: scalar tail */
         /* ---- stage A ---- */
-        int64_t pv[2][BS_R] = {}, skv[BS_R] = {}, lkv[BS_R] = {}, kv[BS_R];
-        if (a.n_preds > 0) d_bs_load_i32(a.pc[0], base, n, full, pv[0]);
-        if (a.n_preds > 1) d_bs_load_i32(a.pc[1], base, n, full, pv[1]);
-        if (a.sk) d_bs_load_i64(a.sk, base, n, full, skv);
-        if (a.lk) d_bs_load_i64(a.lk, base, n, full, lkv);
-        d_bs_load_i64(a.key, base, n, full, kv);
+        int32_t pv[2][BS_R] = {};
+        int64_t skv[BS_R] = {}, lkv[BS_R] = {}, kv[BS_R], pay[BS_R] = {};
+        if (base + BS_R <= n) {
+            if constexpr (NP > 0) d_bs_vload_i32(a.pc[0] + base, pv[0]);
+            if constexpr (NP > 1) d_bs_vload_i32(a.pc[1] + base, pv[1]);
+            if constexpr (SK) d_bs_vload_i64(a.sk + base, skv);
+            if constexpr (LK) d_bs_vload_i64(a.lk + base, lkv);
+            d_bs_vload_i64(a.key + base, kv);
+            if constexpr (OWN_PAY) {
+#pragma unroll
+                for (int j = 0; j < BS_R; j++)
+                    pay[j] = d_bs_pay<PAY>(a.pay, base + j);
+            }
+        } else { /* scalar tail: the last, partial tile of the page */
+#pragma unroll
+            for (int j = 0; j < BS_R; j++) {
+                const bool in = base + j < n;
+                if constexpr (NP > 0) pv[0][j] = in ? a.pc[0][base + j] : 0;
+                if constexpr (NP > 1) pv[1][j] = in ? a.pc[1][base + j] : 0;
+                if constexpr (SK) skv[j] = in ? a.sk[base + j] : 0;
+                if constexpr (LK) lkv[j] = in ? a.lk[base + j] : 0;
+                kv[j] = in ? a.key[base + j] : 0;
+                if constexpr (OWN_PAY)
+                    pay[j] = in ? d_bs_pay<PAY>(a.pay, base + j) : 0;
+            }
+        }
         /* ---- stage B ---- */
         bool ok[BS_R];
 #pragma unroll
         for (int j = 0; j < BS_R; j++) {
             ok[j] = base + j < n;
-            if (a.n_preds > 0)
+            if constexpr (NP > 0)
                 ok[j] = ok[j] && d_cmp_i64(a.pop[0], pv[0][j], a.pval[0]);
-            if (a.n_preds > 1)
+            if constexpr (NP > 1)
                 ok[j] = ok[j] && d_cmp_i64(a.pop[1], pv[1][j], a.pval[1]);
             /* keys outside the dense ranges are dropped before the gather */
-            if (a.lk) ok[j] = ok[j] && lkv[j] >= 1 && lkv[j] <= a.lucap;
-            if (a.sk) ok[j] = ok[j] && skv[j] >= 1 && skv[j] <= a.nflags;
+            if constexpr (LK)
+                ok[j] = ok[j] && lkv[j] >= 1 && lkv[j] <= a.lucap;
+            if constexpr (SK)
+                ok[j] = ok[j] && skv[j] >= 1 && skv[j] <= a.nflags;
         }
+        /* every gather goes out, a dropped row's from index 0 (the host
+         * sees to it that byte 0 exists), and is selected afterwards */
         uint8_t fl[BS_R], plv[BS_R];
-        int64_t pay[BS_R];
 #pragma unroll
         for (int j = 0; j < BS_R; j++) {
-            fl[j] = 1;
-            plv[j] = 0;
-            pay[j] = 0;
-            if (!ok[j]) continue;
-            if (a.sk) fl[j] = a.flags[skv[j] - 1];
-            if (a.lk) plv[j] = a.lu[lkv[j] - 1];
-            else if (a.pay_pred < 0) {
-                if (a.pay_tag == PG_T_I32)
-                    pay[j] = ((const int32_t*)a.pay)[base + j];
-                else if (a.pay_tag == PG_T_U8)
-                    pay[j] = ((const uint8_t*)a.pay)[base + j];
-                else
-                    pay[j] = ((const int64_t*)a.pay)[base + j];
-            }
+            if constexpr (SK) fl[j] = a.flags[ok[j] ? skv[j] - 1 : 0];
+            if constexpr (LK) plv[j] = a.lu[ok[j] ? lkv[j] - 1 : 0];
         }
 #pragma unroll
         for (int j = 0; j < BS_R; j++) {
-            ok[j] = ok[j] && fl[j] != 0;
-            if (a.lk) pay[j] = plv[j];
-            else if (a.pay_pred >= 0)
+            if constexpr (SK) ok[j] = ok[j] && fl[j] != 0;
+            if constexpr (LK) pay[j] = plv[j];
+            else if constexpr (PAY == BS_PAY_PRED)
                 pay[j] = a.pay_pred ? pv[1][j] : pv[0][j];
         }
         /* ---- stage C ---- */
@@ -1721,6 +1754,37 @@ __global__ __launch_bounds__(256) void k_tbl_insert_staged(
         if (my_inserted) atomicAdd(inserted, (unsigned long long)my_inserted);
         if (my_overflow) atomicAdd(overflow, (unsigned long long)my_overflow);
         if (my_packerr) atomicAdd(pack_err, (unsigned long long)my_packerr);
+    }
+}
+/* the instance of k_tbl_insert_staged for a page's shape */
+typedef void (*staged_fn)(staged_args, int32_t, int64_t*, uint8_t*, int64_t,
+                          unsigned long long*, unsigned long long*,
+                          unsigned long long*, unsigned long long*, int64_t,
+                          unsigned long long*);
+template <int NP, bool SK>
+static staged_fn bs_pick_pay(const staged_args& a)
+{
+    if (a.lk) return k_tbl_insert_staged<NP, SK, true, BS_PAY_LOOKUP>;
+    if (a.pay_pred >= 0)
+        return k_tbl_insert_staged<NP, SK, false, BS_PAY_PRED>;
+    switch (a.pay_tag) {
+        case PG_T_I32:
+            return k_tbl_insert_staged<NP, SK, false, BS_PAY_I32>;
+        case PG_T_U8:
+            return k_tbl_insert_staged<NP, SK, false, BS_PAY_U8>;
+        default:
+            return k_tbl_insert_staged<NP, SK, false, BS_PAY_I64>;
+    }
+}
+static staged_fn bs_pick(const staged_args& a)
+{
+    switch (a.n_preds) {
+        case 0:
+            return a.sk ? bs_pick_pay<0, true>(a) : bs_pick_pay<0, false>(a);
+        case 1:
+            return a.sk ? bs_pick_pay<1, true>(a) : bs_pick_pay<1, false>(a);
+        default:
+            return a.sk ? bs_pick_pay<2, true>(a) : bs_pick_pay<2, false>(a);
     }
 }
 
@@ -2265,16 +2329,32 @@ __attribute__((amdgpu_waves_per_eu(7))) void k_probe_agg(
 /* specialized fused probe+agg for the Q3 shape (the codegen-analog
  * specialization, like k_agg_q1): optional single int32 predicate, i64
  * key column, DISC_PRICE(a,b) projection over two f64 columns.
- * Four rows per thread per pass: the key/predicate columns are read with
- * nontemporal vector loads, and the four probe chains advance in
- * LOCKSTEP (a state-machine loop issuing up to four independent tag
- * loads per iteration) — the probe is latency-bound, so memory-level
- * parallelism is the lever.  ep/dc are loaded only for probe hits (~9%
+ * PQ3_Q rows per thread per pass: the key/predicate columns are read with
+ * nontemporal vector loads.  ep/dc are loaded only for probe hits (~9%
  * of rows at SF100): skipping the 16 B money loads on the miss path
  * saves ~5 GB of the 600M-row pass. */
+/* The dependent loads of a pass go out together, row by row of a stage and
+ * not stage by stage of a row: the bitmap words of all rows, then the
+ * first tag and the first key word of all rows.  A row that is not
+ * selected, or whose key is outside [1, bmax], or that the bitmap
+ * rejected, loads word / slot 0 instead and is deselected afterwards, so
+ * no load sits behind a per-row branch (the compiler waits for such a
+ * load before it issues the next).  Only chains longer than one slot,
+ * which are rare at fill 0.5, run one after another.  Whether there is a
+ * bitmap and whether there are tags is the same for the whole launch and
+ * is a template parameter.
+ * Measured (profiles/q3_streams.json): this ordering left the SF100 kernel
+ * where it was (2.10 ms against 2.10 ms), so the kernel is not bound by
+ * the round trips of its dependent loads; four rows per thread (2.13 ms)
+ * and grids of 2048 and 8192 blocks (2.13, 2.09 ms) are inside the same
+ * spread and are not kept.  An earlier 4-row lockstep state machine was
+ * slower than two unrolled chains. */
 /* waves_per_eu(8): 4096 blocks are exactly two rounds at 8 waves per SIMD.
  * The hit-list staging raised scalar-register use past that occupancy;
  * the attribute has the compiler park the cold ones in vector lanes. */
+#define PQ3_Q 2       /* rows per thread and pass */
+#define PQ3_GRID 4096 /* blocks */
+template <bool KB, bool TAGS>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(8))) void k_probe_agg_q3(
     const int32_t* sd /* nullable pred col */, int32_t pred_op,
@@ -2287,10 +2367,7 @@ __attribute__((amdgpu_waves_per_eu(8))) void k_probe_agg_q3(
 {
     typedef int vi2 __attribute__((ext_vector_type(2)));
     typedef long vl2 __attribute__((ext_vector_type(2)));
-    const int Q = 2; /* measured: 2-row unrolled chains beat a 4-row
-                        lockstep state machine (most probes resolve in one
-                        step, so the machinery costs more than the extra
-                        memory-level parallelism buys) */
+    const int Q = PQ3_Q;
     int64_t base0 = Q * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
     int64_t stride = Q * (int64_t)gridDim.x * blockDim.x;
     const int lane = threadIdx.x & 63;
@@ -2315,14 +2392,22 @@ __attribute__((amdgpu_waves_per_eu(8))) void k_probe_agg_q3(
     for (int64_t base = base0; base - Q * lane < n + stride;
          base += stride) {
         int64_t k[Q];
-        int32_t s[Q];
+        int32_t s[Q] = {};
         bool sel[Q];
         if (base + Q <= n) {
-            vl2 ka = __builtin_nontemporal_load((const vl2*)(okey + base));
-            k[0] = ka[0]; k[1] = ka[1];
+#pragma unroll
+            for (int j = 0; j < Q; j += 2) {
+                vl2 ka = __builtin_nontemporal_load(
+                    (const vl2*)(okey + base + j));
+                k[j] = ka[0]; k[j + 1] = ka[1];
+            }
             if (sd) {
-                vi2 ss = __builtin_nontemporal_load((const vi2*)(sd + base));
-                s[0] = ss[0]; s[1] = ss[1];
+#pragma unroll
+                for (int j = 0; j < Q; j += 2) {
+                    vi2 ss = __builtin_nontemporal_load(
+                        (const vi2*)(sd + base + j));
+                    s[j] = ss[0]; s[j + 1] = ss[1];
+                }
             }
 #pragma unroll
             for (int j = 0; j < Q; j++) sel[j] = true;
@@ -2340,31 +2425,51 @@ __attribute__((amdgpu_waves_per_eu(8))) void k_probe_agg_q3(
                 sel[j] = sel[j] && (pred_op == PG_CMP_GT ? s[j] > pred_val
                                                          : s[j] < pred_val);
         }
+        /* dynamic-filter bitmap: one (usually L3-hot) load rejects ~91% of
+         * rows before the hash + tag/key chain */
+        if constexpr (KB) {
+            unsigned long long w[Q];
+#pragma unroll
+            for (int j = 0; j < Q; j++) {
+                sel[j] = sel[j] && (uint64_t)(k[j] - 1) < (uint64_t)bmax;
+                w[j] = kbits[sel[j] ? (uint64_t)k[j] >> 6 : 0];
+            }
+#pragma unroll
+            for (int j = 0; j < Q; j++)
+                sel[j] = sel[j] && ((w[j] >> (k[j] & 63)) & 1);
+        }
+        /* with tags and no bitmap the tags are what rejects a miss: the
+         * key word is then read behind a matching tag only */
+        constexpr bool KEY_WITH_TAG = KB || !TAGS;
+        int64_t p[Q], kw[Q];
+        uint8_t tg[Q], t[Q];
+#pragma unroll
+        for (int j = 0; j < Q; j++) {
+            uint64_t h = pg_murmur3_finalize(pg_bigint_hash(k[j]));
+            p[j] = sel[j] ? (int64_t)(h & (uint64_t)mask) : 0;
+            tg[j] = d_tbl_tag(h);
+            t[j] = 0;
+            kw[j] = 0;
+            if constexpr (TAGS) t[j] = tags[p[j]];
+            if constexpr (KEY_WITH_TAG) kw[j] = keys[p[j]];
+        }
         int64_t slot[Q];
 #pragma unroll
         for (int j = 0; j < Q; j++) {
             slot[j] = -1;
             if (!sel[j]) continue;
-            /* dynamic-filter bitmap: one (usually L3-hot) load rejects
-             * ~91% of rows before the hash + tag/key chain */
-            if (kbits && !d_kbit_test(kbits, bmax, k[j])) continue;
-            uint64_t h = pg_murmur3_finalize(pg_bigint_hash(k[j]));
-            int64_t p = (int64_t)(h & (uint64_t)mask);
-            uint8_t tg = tags ? d_tbl_tag(h) : 0;
             for (;;) {
-                if (tags) {
-                    uint8_t t = tags[p];
-                    if (t == 0) break;
-                    if (t == tg && (keys[p] >> pbits) == k[j]) {
-                        slot[j] = p;
+                if (TAGS ? t[j] == 0 : kw[j] == TBL_EMPTY) break;
+                if (!TAGS || t[j] == tg[j]) {
+                    if constexpr (!KEY_WITH_TAG) kw[j] = keys[p[j]];
+                    if ((kw[j] >> pbits) == k[j]) {
+                        slot[j] = p[j];
                         break;
                     }
-                } else {
-                    int64_t kw = keys[p];
-                    if (kw == TBL_EMPTY) break;
-                    if ((kw >> pbits) == k[j]) { slot[j] = p; break; }
                 }
-                p = d_probe_next(p, lmask);
+                p[j] = d_probe_next(p[j], lmask);
+                if constexpr (TAGS) t[j] = tags[p[j]];
+                if constexpr (KEY_WITH_TAG) kw[j] = keys[p[j]];
             }
         }
         if (hl.ents) {
@@ -6189,9 +6294,16 @@ struct BuildOp : Op {
              * builds the tag store lands in the L3-resident region wave
              * (nearly free), so enable them there unconditionally.
              * A tight fill_x10 declares always-hit probes (no misses to
-             * reject): skip the tag array and its random stores. */
+             * reject): skip the tag array and its random stores.
+             * A key bitmap is an exact membership test (a bit is set if
+             * and only if the key went in; keys outside its range raise),
+             * so a probe that passed it is a hit and the tags could
+             * reject nothing: a non-partitioned build with a bitmap skips
+             * them as well. */
             bool always_hit = plan.fill_x10 >= 11 && plan.fill_x10 < 20;
-            if (!always_hit && (part || cap >= (64ll << 20))) {
+            bool exact_bitmap = !part && plan.bitmap_max_key > 0;
+            if (!always_hit && !exact_bitmap &&
+                (part || cap >= (64ll << 20))) {
                 t->tags.alloc((size_t)cap);
                 if (!part) t->tags.zero(); /* part: k_part_insert inits */
             }
@@ -6509,11 +6621,23 @@ struct BuildOp : Op {
             staged_args sa;
             if (staged_fit(sp.pg, semi, lu, &sa)) {
                 int64_t tiles = (sa.n + BS_TILE - 1) / BS_TILE;
-                int grid = (int)(tiles < 4096 ? (tiles > 0 ? tiles : 1)
-                                              : 4096);
+                int64_t cap_grid = BS_GRID;
+                /* PG_STAGED_GRID caps the grid (tests: several tiles per
+                 * block at a few thousand rows) */
+                if (const char* eg = getenv("PG_STAGED_GRID"))
+                    if (atoi(eg) > 0) cap_grid = atoi(eg);
+                int grid = (int)(tiles < cap_grid ? (tiles > 0 ? tiles : 1)
+                                                  : cap_grid);
+                /* the clamped gathers of dropped rows read byte 0: an
+                 * empty dense range gets a byte that exists (every row is
+                 * dropped, so its value is never looked at) */
+                if (sa.sk && sa.nflags <= 0)
+                    sa.flags = (const uint8_t*)counters.p;
+                if (sa.lk && sa.lucap <= 0)
+                    sa.lu = (const uint8_t*)counters.p;
                 hot_begin();
                 hipLaunchKernelGGL(
-                    k_tbl_insert_staged, dim3(grid), dim3(256), 0, g_stream,
+                    bs_pick(sa), dim3(grid), dim3(256), 0, g_stream,
                     sa, plan.pack_bits, (int64_t*)t->keys.p,
                     (uint8_t*)t->tags.p, t->mask,
                     (unsigned long long*)counters.p,
@@ -7217,8 +7341,19 @@ struct JoinOp : Op {
             hot_begin();
             if (spec) {
                 const pg_pred& pr = plan.preds[0];
+                auto kern =
+                    t->kbits.p
+                        ? (t->tags.p ? k_probe_agg_q3<true, true>
+                                     : k_probe_agg_q3<true, false>)
+                        : (t->tags.p ? k_probe_agg_q3<false, true>
+                                     : k_probe_agg_q3<false, false>);
+                /* PG_PROBE_GRID caps the grid (tests: several passes per
+                 * block at a few thousand rows) */
+                int grid = PQ3_GRID;
+                if (const char* eg = getenv("PG_PROBE_GRID"))
+                    if (atoi(eg) > 0) grid = atoi(eg);
                 hipLaunchKernelGGL(
-                    k_probe_agg_q3, dim3(4096), dim3(256), 0, g_stream,
+                    kern, dim3(grid), dim3(256), 0, g_stream,
                     plan.n_preds
                         ? (const int32_t*)sp.pg.cols[pr.col].data
                         : nullptr,
@@ -9197,6 +9332,15 @@ extern "C" pg_status pg_table_destroy(int64_t t)
     std::lock_guard<std::mutex> lk(g_mu);
     g_tables.erase(t);
     return PG_OK;
+}
+
+/* bytes of the table's tag array; 0: no tags (or no such table) */
+extern "C" int64_t pg_table_tag_bytes(int64_t t)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    auto it = g_tables.find(t);
+    if (it == g_tables.end()) return 0;
+    return it->second->tags.p ? (int64_t)it->second->tags.sz : 0;
 }
 
 extern "C" pg_status pg_table_reset_acc(int64_t t)
